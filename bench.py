@@ -14,7 +14,13 @@ enclosure with W x 1e8 rays in total (weak scaling: 1e8 rays per GPU).  There
 is no data-path collective; a gloo barrier brackets the timed region and the
 elapsed time is max-reduced over ranks.
 
-Prints one JSON line on rank 0.
+A plain run sets up, warms up, times the K steps and prints one JSON line on
+rank 0 (metric, value, ms_per_step and the timed steps' own checks).
+--dump-outputs DIR also writes what the last timed step computed (rank 0's
+count matrix, see dump_outputs).  Everything else the benchmark measures --
+kernel time and the rooflines, the faithful-sampling and Philox-10 legs, the
+PCIe-inclusive passes, the CPU baseline -- takes runs of its own after the
+timed steps and is reported only with --full.
 """
 from __future__ import annotations
 
@@ -290,6 +296,41 @@ def read_valu_issue_per_ray():
         return None
 
 
+DUMP_ROWS = 256          # rows of the count matrix written densely by --dump-outputs
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(outdir, res, begin, stride):
+    """Write what the last timed step left in `res` -- the CSR of counts a
+    caller of rthx_trace_exchange reads back (rthx_result_copy_csr) -- as
+    float64 .npy files in `outdir`, 22 MB in all for the 10605-emitter
+    workload (the whole CSR would be 30e6 entries):
+      row_ptr.npy      [N + 1]  the CSR row pointers, whole
+      row_totals.npy   [N]      rays tallied per emitter row (sum of its counts)
+      col_totals.npy   [N]      counts summed per absorber over every row
+      sample_rows.npy  [S]      S = min(DUMP_ROWS, rows traced) emitter rows, a fixed
+                                seeded choice among the rows of this shard (begin, stride)
+      sample_counts.npy [S][N]  those rows of the count matrix, dense
+    Counts are integers below 2^32, exact in float64; a trace is a pure
+    function of (domain, R, seed, row), so two builds can be compared file by
+    file."""
+    row_ptr, cols, counts = res.csr()
+    n = len(row_ptr) - 1
+    csum = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+    traced = np.arange(begin, n, stride)
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    rows = np.sort(rng.choice(traced, size=min(DUMP_ROWS, len(traced)), replace=False))
+    dense = np.zeros((len(rows), n), dtype=np.float64)
+    for k, g in enumerate(rows):
+        s = slice(row_ptr[g], row_ptr[g + 1])
+        dense[k, cols[s]] = counts[s]
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in (("row_ptr", row_ptr), ("row_totals", csum[row_ptr[1:]] - csum[row_ptr[:-1]]),
+                    ("col_totals", np.bincount(cols, weights=counts, minlength=n)),
+                    ("sample_rows", rows), ("sample_counts", dense)):
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def _spawn_ranks(n):
     """`python bench.py --gpus N` started as a plain process: launch the N
     ranks with torch.distributed.run as a child (before this process touches
@@ -317,6 +358,13 @@ def main():
                          "the steady-state GPU clock (the first ~15 steps of a fresh process run up to 20%% slower)")
     ap.add_argument("--rays-per-gpu", type=int, default=RAYS_PER_GPU)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's count matrix: row "
+                         "pointers, row and column totals, a fixed seeded sample of rows) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: kernel time and the "
+                         "rooflines, blocking steps, the faithful-sampling and Philox-10 legs, the PCIe-inclusive "
+                         "passes and the CPU baseline (the options below select among them)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--mode", choices=("ranks", "threads"), default="ranks",
@@ -457,20 +505,24 @@ def main():
         info = res.info()
         steps_checked = args.steps
         timed_mode = "blocking calls (fallback: pipelined steps faulted)"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, targs.emitter_begin, targs.emitter_stride)
     # Kernel time per launch (HIP events) and the blocking-call rate, from
     # blocking steps after the timed region (the roofline's avg kernel time)
     trace_ms = []
     pack_ms = []
-    n_blk = max(5, min(args.steps, 20))
-    sync_all()
-    tb = time.perf_counter()
-    for _ in range(n_blk):
-        res.trace(dd, targs)
-        ib = res.info()
-        trace_ms.append(ib["trace_ms"])
-        pack_ms.append(ib["pack_ms"])
-    sync_all()
-    blocking_ms = (time.perf_counter() - tb) / n_blk * 1e3
+    blocking_ms = None
+    if args.full:
+        n_blk = max(5, min(args.steps, 20))
+        sync_all()
+        tb = time.perf_counter()
+        for _ in range(n_blk):
+            res.trace(dd, targs)
+            ib = res.info()
+            trace_ms.append(ib["trace_ms"])
+            pack_ms.append(ib["pack_ms"])
+        sync_all()
+        blocking_ms = (time.perf_counter() - tb) / n_blk * 1e3
 
     rays_rank = info["rays_traced"]
     nnz_rank = info["nnz"]
@@ -490,7 +542,7 @@ def main():
     # emitVolumeRay2D.jl:26-31, Float32 Lambert draws), same launch otherwise;
     # reported beside `value`, never as it.
     faithful = None
-    if rank == 0 and args.faithful_steps > 0:
+    if args.full and rank == 0 and args.faithful_steps > 0:
         fargs, _kf = _lib.make_args(0, R, nudge, args.seed, targs.emitter_begin, N, targs.emitter_stride,
                                     device=device, flags=abi.RTHX_FLAG_DEVICE_ONLY | abi.RTHX_FLAG_FAITHFUL_SAMPLING)
         for _ in range(3):
@@ -510,7 +562,7 @@ def main():
                     "gpus": 1, "note": "faithful sampling (RTHX_FLAG_FAITHFUL_SAMPLING), rank 0's launch"}
 
     p10 = None
-    if rank == 0 and args.philox10_steps > 0:
+    if args.full and rank == 0 and args.philox10_steps > 0:
         p10 = philox10_leg(flat, R, nudge, args.seed, targs.emitter_begin, targs.emitter_stride,
                            args.philox10_steps, device)
 
@@ -519,7 +571,7 @@ def main():
     # caller reuses across traces (rthx_host_register), and the same with F_raw
     # (counts normalised on the device, rthx_result_copy_F) instead of counts.
     e2e = e2e_F = None
-    if rank == 0:
+    if args.full and rank == 0:
         pin = _lib.PinnedArrays()
         args_h, _kh = _lib.make_args(0, R, nudge, args.seed, targs.emitter_begin, N, targs.emitter_stride,
                                      device=device)
@@ -543,37 +595,10 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = rays_all * args.steps / elapsed / 1e6
-        avg_trace_ms = float(np.mean(trace_ms))
         # B_alg = 8 B/ray + 12 B x nnz/(N R), per GPU (in
         # threads mode one result covers every device: per-device share)
         per = n_units if args.mode == "threads" else 1
         rays_rank, nnz_rank = rays_rank / per, nnz_rank / per
-        b_alg = 8.0 * rays_rank + 12.0 * nnz_rank
-        achieved = b_alg / (avg_trace_ms * 1e-3) / 1e9
-        # the committed PMC traffic was measured on the 1-GPU launch; other
-        # shard shapes (row-split launches) are not covered by it
-        traffic = read_pmc_traffic() if n_units == 1 else None
-        fpr = read_fp64_flops_per_ray()
-        fp64_roof = None
-        if fpr is not None:
-            tf = rays_rank * fpr / (avg_trace_ms * 1e-3) / 1e12
-            fp64_roof = {"bound": "fp64-valu", "achieved": round(tf, 3), "peak": FP64_VECTOR_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(tf / FP64_VECTOR_PEAK_TFLOPS, 4),
-                         "flop_per_ray": round(fpr, 1),
-                         "note": f"fp64 VALU instructions per ray from {os.path.relpath(profile_file('pmc_sq.json'), ROOT)} (SQ counters)"}
-        vi = read_valu_issue_per_ray()
-        valu_roof = None
-        if vi is not None:
-            per_ray_s, eq_per_wave_ray, peak_rate = vi
-            floor_ms = rays_rank * per_ray_s * 1e3
-            ach = rays_rank / 64.0 * eq_per_wave_ray / (avg_trace_ms * 1e-3)
-            valu_roof = {"bound": "valu-issue", "achieved": round(ach / 1e9, 2), "peak": round(peak_rate / 1e9, 2),
-                         "unit": "G wave-instr/s (v_fma_f64-equivalent)", "frac": round(floor_ms / avg_trace_ms, 4),
-                         "issue_floor_ms": round(floor_ms, 4),
-                         "note": (f"SQ instruction counts ({os.path.relpath(profile_file('pmc_sq.json'), ROOT)}) "
-                                  "priced at the issue rates tools/probe/valu_probe.hip measured "
-                                  f"({os.path.relpath(profile_file('valu_probe.json'), ROOT)}): the binding "
-                                  "roofline of this kernel")}
         out = {
             "metric": METRIC,
             "value": round(value, 3),
@@ -602,40 +627,70 @@ def main():
                 "devices_visible": ndev,
                 "seed": args.seed,
                 "rng": ("Philox4x32-7 blocks, counter (emitter, ray, draw), key (seed, bin); 32-bit uniform draws "
-                        "(DESIGN.md §5); the 10-round build is timed in `philox10`"),
+                        "(DESIGN.md §5); with --full the 10-round build is timed in `philox10`"),
             },
-            "roofline": {
-                "bound": "hbm",
-                "achieved": round(achieved, 3),
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 6),
-                "traffic": traffic,
-                "kernel": TRACE_KERNEL,
-                "avg_kernel_ms": round(avg_trace_ms, 4),
-                "alg_bytes_per_launch": b_alg,
-                "note": "VALU-issue bound path (roofline_valu); HBM fraction reported as mandated (DESIGN.md §6)",
-            },
-            "pack_ms": round(float(np.mean(pack_ms)), 4),
             "step_mode": timed_mode,
             "steps_checked": steps_checked,
             "pipelined_step_faults": step_faults,
-            "blocking_ms_per_step": round(blocking_ms, 4),
-            "roofline_fp64": fp64_roof,
-            "roofline_valu": valu_roof,
-            "faithful_sampling": faithful,
-            "philox10": p10,
-            "e2e_with_d2h_mrays_s": round(e2e, 3) if e2e else None,
-            "e2e_F_with_d2h_mrays_s": round(e2e_F, 3) if e2e_F else None,
         }
         if args.emulate_world > 1:
             out["emulated_rank0_of"] = world
             out["value"] = None  # one rank's shard only: not a whole-job measurement
             out["rank0_mrays_s"] = round(rays_rank * args.steps / elapsed / 1e6, 3)
-        if n_units == 1 and not args.no_cpu:
-            out["cpu_baseline"] = cpu_baseline(dom, R, nudge, args.seed, args.cpu_budget)
-        else:
-            out["cpu_baseline"] = None
+        if args.full:
+            avg_trace_ms = float(np.mean(trace_ms))
+            b_alg = 8.0 * rays_rank + 12.0 * nnz_rank
+            achieved = b_alg / (avg_trace_ms * 1e-3) / 1e9
+            # the committed PMC traffic was measured on the 1-GPU launch; other
+            # shard shapes (row-split launches) are not covered by it
+            traffic = read_pmc_traffic() if n_units == 1 else None
+            fpr = read_fp64_flops_per_ray()
+            fp64_roof = None
+            if fpr is not None:
+                tf = rays_rank * fpr / (avg_trace_ms * 1e-3) / 1e12
+                fp64_roof = {"bound": "fp64-valu", "achieved": round(tf, 3), "peak": FP64_VECTOR_PEAK_TFLOPS,
+                             "unit": "TFLOP/s", "frac": round(tf / FP64_VECTOR_PEAK_TFLOPS, 4),
+                             "flop_per_ray": round(fpr, 1),
+                             "note": f"fp64 VALU instructions per ray from {os.path.relpath(profile_file('pmc_sq.json'), ROOT)} (SQ counters)"}
+            vi = read_valu_issue_per_ray()
+            valu_roof = None
+            if vi is not None:
+                per_ray_s, eq_per_wave_ray, peak_rate = vi
+                floor_ms = rays_rank * per_ray_s * 1e3
+                ach = rays_rank / 64.0 * eq_per_wave_ray / (avg_trace_ms * 1e-3)
+                valu_roof = {"bound": "valu-issue", "achieved": round(ach / 1e9, 2), "peak": round(peak_rate / 1e9, 2),
+                             "unit": "G wave-instr/s (v_fma_f64-equivalent)", "frac": round(floor_ms / avg_trace_ms, 4),
+                             "issue_floor_ms": round(floor_ms, 4),
+                             "note": (f"SQ instruction counts ({os.path.relpath(profile_file('pmc_sq.json'), ROOT)}) "
+                                      "priced at the issue rates tools/probe/valu_probe.hip measured "
+                                      f"({os.path.relpath(profile_file('valu_probe.json'), ROOT)}): the binding "
+                                      "roofline of this kernel")}
+            out.update({
+                "roofline": {
+                    "bound": "hbm",
+                    "achieved": round(achieved, 3),
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 6),
+                    "traffic": traffic,
+                    "kernel": TRACE_KERNEL,
+                    "avg_kernel_ms": round(avg_trace_ms, 4),
+                    "alg_bytes_per_launch": b_alg,
+                    "note": "VALU-issue bound path (roofline_valu); HBM fraction reported as mandated (DESIGN.md §6)",
+                },
+                "pack_ms": round(float(np.mean(pack_ms)), 4),
+                "blocking_ms_per_step": round(blocking_ms, 4),
+                "roofline_fp64": fp64_roof,
+                "roofline_valu": valu_roof,
+                "faithful_sampling": faithful,
+                "philox10": p10,
+                "e2e_with_d2h_mrays_s": round(e2e, 3) if e2e else None,
+                "e2e_F_with_d2h_mrays_s": round(e2e_F, 3) if e2e_F else None,
+            })
+            if n_units == 1 and not args.no_cpu:
+                out["cpu_baseline"] = cpu_baseline(dom, R, nudge, args.seed, args.cpu_budget)
+            else:
+                out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     res.close()
     dd.close()

@@ -11,7 +11,7 @@ P7=raytraceheattransfer.jl_amd/csrc/_ab/p7/librthx.so
 for r in 1 2 3; do
   for v in "philox10 $IN" "philox7 $P7"; do
     set -- $v
-    RTHX_LIB=$2 timeout -k 10 200 python bench.py --no-cpu --faithful-steps 0 --steps 30 > $O/ab_$1_$r.json 2>/dev/null || exit 1
+    RTHX_LIB=$2 timeout -k 10 200 python bench.py --full --no-cpu --faithful-steps 0 --steps 30 > $O/ab_$1_$r.json 2>/dev/null || exit 1
     python -c "
 import json; d=json.loads(open('$O/ab_$1_$r.json').read().strip().splitlines()[-1])
 print('$1', 'value', d['value'], 'ms', d['ms_per_step'], 'kernel', d['roofline']['avg_kernel_ms'])" | tee -a $O/ab_philox.log

@@ -6,7 +6,7 @@ set -o pipefail
 mkdir -p gpurun_out
 for W in 1 2 4 8; do
   if [ $W = 1 ]; then extra=""; else extra="--emulate-world $W"; fi
-  timeout -k 10 200 python bench.py --no-cpu --faithful-steps 0 --steps 20 --warmup 5 $extra 2>/dev/null | tail -1 | python -c "
+  timeout -k 10 200 python bench.py --full --no-cpu --faithful-steps 0 --steps 20 --warmup 5 $extra 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 c = d['config']

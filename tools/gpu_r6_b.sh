@@ -26,7 +26,9 @@ grep -E "passed|failed" gpurun_out/r6/pytest_acc.log | tail -2
 RTHX_ACCURACY_RECORD=gpurun_out/r6/accuracy.json timeout -k 10 600 python -u -m pytest -x -q -s --timeout 400 --timeout-method thread -m gpu \
   "tests/test_gpu_accuracy.py::test_f_smooth_rms_vs_1e9_ray_reference" > gpurun_out/r6/pytest_acc_rec.log 2>&1 || exit 1
 grep RMS gpurun_out/r6/pytest_acc_rec.log
-timeout -k 10 400 python bench.py > gpurun_out/r6/bench_a.json 2> gpurun_out/r6/bench_a.err || { tail gpurun_out/r6/bench_a.err; exit 1; }
+LOGS=${LOGS:-logs}
+mkdir -p $LOGS
+timeout -k 10 600 python bench.py --full > $LOGS/bench_a.json 2> $LOGS/bench_a.err || { tail $LOGS/bench_a.err; exit 1; }
 python -c "
-import json; d = json.load(open('gpurun_out/r6/bench_a.json'))
+import json; d = json.load(open('$LOGS/bench_a.json'))
 print('value', d['value'], 'kernel', d['roofline']['avg_kernel_ms'], 'philox10', d['philox10'], 'faithful', d['faithful_sampling']['value'])"

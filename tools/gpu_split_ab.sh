@@ -12,13 +12,15 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_bo
   --timeout 120 --timeout-method thread -p no:cacheprovider -k "split or shard or lookback or c1" \
   > gpurun_out/pt_$TAG.log 2>&1 || { tail -40 gpurun_out/pt_$TAG.log; exit 1; }
 tail -n 1 gpurun_out/pt_$TAG.log
+LOGS=${LOGS:-logs}  # (bench.py's stderr is kept there)
+mkdir -p $LOGS
 for S in $SETS; do
   export RTHX_SPLIT_BELOW=${S%%:*} RTHX_SPLIT_TARGET=${S##*:}
   for MODE in strong weak; do
     for W in 1 2 4 8; do
       if [ $W = 1 ]; then extra=""; else extra="--emulate-world $W"; fi
       if [ $MODE = strong ]; then extra="$extra --strong"; fi
-      timeout -k 10 120 python bench.py --no-cpu --faithful-steps 0 --steps 50 --warmup 10 $extra 2>>gpurun_out/split_$TAG.err \
+      timeout -k 10 120 python bench.py --full --no-cpu --faithful-steps 0 --steps 50 --warmup 10 $extra 2>>$LOGS/split_$TAG.err \
         | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())

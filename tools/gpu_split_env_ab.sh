@@ -7,13 +7,15 @@ WS=${1:-"4 8"}
 MODES=${2:-"strong weak"}
 IFS=';' read -ra ENVS <<< "${3:--}"
 EXTRA=${4:-}
+LOGS=${LOGS:-logs}  # (bench.py's stderr is kept there)
+mkdir -p $LOGS
 for E in "${ENVS[@]}"; do
   for MODE in $MODES; do
     for W in $WS; do
       if [ $W = 1 ]; then extra=""; else extra="--emulate-world $W"; fi
       if [ $MODE = strong ]; then extra="$extra --strong"; fi
       envs=""; [ "$E" != "-" ] && envs="$E"
-      env $envs timeout -k 10 120 python bench.py --no-cpu --faithful-steps 0 --steps 50 --warmup 10 $extra $EXTRA 2>>gpurun_out/split_env.err \
+      env $envs timeout -k 10 120 python bench.py --full --no-cpu --faithful-steps 0 --steps 50 --warmup 10 $extra $EXTRA 2>>$LOGS/split_env.err \
         | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())

@@ -6,7 +6,7 @@
 set -o pipefail
 for W in 1 2 4 8; do
   if [ $W = 1 ]; then extra=""; else extra="--emulate-world $W"; fi
-  timeout -k 10 120 python bench.py --strong --no-cpu --faithful-steps 0 --steps 50 --warmup 10 $extra 2>/dev/null \
+  timeout -k 10 120 python bench.py --full --strong --no-cpu --faithful-steps 0 --steps 50 --warmup 10 $extra 2>/dev/null \
     | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
