@@ -23,6 +23,7 @@
 
 #include "rthx_device.h"
 #include "rthx_kernels.h"
+#include "rthx_partition.h"
 #include "rthx_wave.h"
 
 namespace rthx {
@@ -183,61 +184,98 @@ __device__ __forceinline__ uint64_t lookback_offset_wave(unsigned long long* sta
 // Workgroup-wide compaction of one row's counts, ascending absorber order
 // (the reference's sparse() sorts columns, parallelRayTracing.jl:154).
 // count2(w, lo, hi) gives the counts of absorbers 2w and 2w+1 (PAIRS) or of w
-// (hi = 0).  Wave v owns a contiguous quarter of the words and walks it 64
-// words per step: a counting pass (ballot + popcount, no barrier), one
-// barrier to combine the four wave totals, then a writing pass whose lanes
-// store consecutive entries (coalesced).  Returns the row's nnz (valid in
-// every lane).
+// (hi = 0).  Wave v owns a contiguous share of the words (wave_word_range,
+// rthx_partition.h) and walks it 64 words per step: a counting pass (ballot +
+// popcount, no barrier), one barrier to combine the wave totals, then a
+// writing pass whose lanes store consecutive entries (coalesced).  Returns
+// the row's nnz (valid in every lane).
+// Everything a wave shares is scalar: its range and step count (the wave
+// index by readfirstlane), the running entry base, the row's two output
+// pointers.  A lane's entry is the running base counted up through the
+// step's two ballots (v_mbcnt), and its stores are row pointer + a 32-bit
+// byte offset.  The writing pass reads its words again: keeping the counting
+// pass's counts in registers (an unrolled 11-step share at the headline
+// shape) measured 0.4 % slower than the two short loops
+// (profiles/round7/ab/row_compaction.log).
 // base_of(row nnz), called by every lane after the counting pass, gives the
 // row's output offset (0 for staging slots; the look-back for the direct CSR).
+__device__ __forceinline__ void store_u32_at(uint32_t* row, uint32_t byte_off, uint32_t v) {
+  *(uint32_t*)((char*)row + byte_off) = v;
+}
+
 template <bool PAIRS, class F, class B>
-__device__ __forceinline__ uint32_t compact_row(int64_t n_words, F count2, uint32_t* __restrict__ out_c_,
+__device__ __forceinline__ uint32_t compact_row(uint32_t n_words, F count2, uint32_t* __restrict__ out_c_,
                                                 uint32_t* __restrict__ out_n_, uint32_t* wave_sum, B base_of,
                                                 uint64_t cap = ~0ull) {
-  const int kWaves = (int)(blockDim.x >> 6);
-  const uint32_t lane = lane_id();
-  const int wave = threadIdx.x >> 6;
-  const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  const int64_t per = ((n_words + kWaves * 64 - 1) / (kWaves * 64)) * 64;
-  const int64_t wb = wave * per;
-  const int64_t we = wb + per < n_words ? wb + per : n_words;
-  uint32_t cnt = 0;
-  for (int64_t w0 = wb; w0 < we; w0 += 64) {
-    const int64_t w = w0 + lane;
-    uint32_t lo = 0u, hi = 0u;
-    if (w < we) count2(w, lo, hi);
-    cnt += __popcll(__ballot(lo != 0u)) + (PAIRS ? __popcll(__ballot(hi != 0u)) : 0);
+  const uint32_t n_waves = blockDim.x >> 6;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const WordRange rg = wave_word_range(n_words, n_waves, wave);
+  const uint32_t wl = rg.wb + lane_id();  // the lane's word of step 0
+  // Only a range's last step can be partial: the steps before it read their
+  // words unmasked.
+  const uint32_t n_full = rg.steps ? rg.steps - 1u : 0u;
+  const uint32_t w_last = wl + 64u * n_full;
+  uint32_t llo = 0u, lhi = 0u;  // the last step's counts
+
+  auto nnz_step = [&](uint32_t lo, uint32_t hi) -> uint32_t {
+    return (uint32_t)__popcll(__ballot(lo != 0u)) + (PAIRS ? (uint32_t)__popcll(__ballot(hi != 0u)) : 0u);
+  };
+  if (w_last < rg.we) count2(w_last, llo, lhi);  // (an empty range: no lane)
+  uint32_t cnt = nnz_step(llo, lhi);
+  for (uint32_t s = n_full, w = wl; s != 0u; --s, w += 64u) {
+    uint32_t lo, hi;
+    count2(w, lo, hi);
+    cnt += nnz_step(lo, hi);
   }
-  if (lane == 0) wave_sum[wave] = cnt;
+  if (lane_id() == 0) wave_sum[wave] = cnt;
   __syncthreads();
-  uint32_t base = 0, total = 0;
-  for (int i = 0; i < kWaves; ++i) {
+  uint32_t before = 0, total = 0;
+  for (uint32_t i = 0; i < n_waves; ++i) {
     const uint32_t ws = wave_sum[i];
-    base += i < wave ? ws : 0u;
+    before += i < wave ? ws : 0u;
     total += ws;
   }
-  const uint64_t gbase = base_of(total);
-  uint32_t* __restrict__ out_c = out_c_ + gbase;
-  uint32_t* __restrict__ out_n = out_n_ + gbase;
-  // (a row that would end past the `cap` entries reserved writes nothing:
-  // base_of has flagged the overflow and the host re-traces)
-  for (int64_t w0 = wb; w0 < (gbase + total <= cap ? we : wb); w0 += 64) {
-    const int64_t w = w0 + lane;
-    uint32_t lo = 0u, hi = 0u;
-    if (w < we) count2(w, lo, hi);
+  total = (uint32_t)__builtin_amdgcn_readfirstlane((int)total);
+  uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane((int)before);  // entries of the row before this step
+  const uint64_t gb = base_of(total);  // (the same in every lane of the workgroup)
+  const uint64_t gbase = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(gb >> 32)) << 32) |
+                         (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)gb);
+  uint32_t* const out_c = out_c_ + gbase;
+  uint32_t* const out_n = out_n_ + gbase;
+  auto write_step = [&](uint32_t w, uint32_t lo, uint32_t hi) {
     const uint64_t m_lo = __ballot(lo != 0u);
     const uint64_t m_hi = PAIRS ? __ballot(hi != 0u) : 0ull;
-    uint32_t pos = base + __popcll(m_lo & lt_mask) + __popcll(m_hi & lt_mask);
-    if (lo) { out_c[pos] = PAIRS ? (uint32_t)(2 * w) : (uint32_t)w; out_n[pos] = lo; ++pos; }
-    if (PAIRS && hi) { out_c[pos] = (uint32_t)(2 * w + 1); out_n[pos] = hi; }
-    base += __popcll(m_lo) + __popcll(m_hi);
+    // the lane's first entry: the base + the entries of the lanes below it
+    uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m_lo >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_lo, base));
+    if (PAIRS) pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m_hi >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_hi, pos));
+    const uint32_t off = pos << 2;  // (bytes; a row has at most 81920 entries)
+    if (lo) {
+      store_u32_at(out_c, off, PAIRS ? 2u * w : w);
+      store_u32_at(out_n, off, lo);
+    }
+    if (PAIRS && hi) {
+      const uint32_t off_hi = off + ((uint32_t)(lo != 0u) << 2);
+      store_u32_at(out_c, off_hi, 2u * w + 1u);
+      store_u32_at(out_n, off_hi, hi);
+    }
+    base += (uint32_t)__popcll(m_lo) + (uint32_t)__popcll(m_hi);
+  };
+  // (a row that would end past the `cap` entries reserved writes nothing:
+  // base_of has flagged the overflow and the host re-traces)
+  if (gbase + total <= cap && rg.steps != 0u) {
+    for (uint32_t s = n_full, w = wl; s != 0u; --s, w += 64u) {
+      uint32_t lo, hi;
+      count2(w, lo, hi);
+      write_step(w, lo, hi);
+    }
+    write_step(w_last, llo, lhi);
   }
   __syncthreads();  // wave_sum may be reused by the caller
   return total;
 }
 
 template <bool PAIRS, class F>
-__device__ __forceinline__ uint32_t compact_row(int64_t n_words, F count2, uint32_t* __restrict__ out_c,
+__device__ __forceinline__ uint32_t compact_row(uint32_t n_words, F count2, uint32_t* __restrict__ out_c,
                                                 uint32_t* __restrict__ out_n, uint32_t* wave_sum) {
   return compact_row<PAIRS>(n_words, count2, out_c, out_n, wave_sum, [](uint32_t) { return (uint64_t)0; });
 }
@@ -945,7 +983,7 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
     }
   }
   const bool from_slabs = SPLIT && PACK16 && tail && __builtin_amdgcn_readfirstlane((int)(s_merge & 2u)) != 0;
-  auto count2 = [&](int64_t w, uint32_t& lo, uint32_t& hi) {
+  auto count2 = [&](uint32_t w, uint32_t& lo, uint32_t& hi) {
     if (SPLIT && PACK16 && from_slabs) {  // (rare: R >= 65536 and one absorber took 65536 of them)
       lo = hi = 0u;
       for (uint32_t p = 0; p < parts; ++p) {
@@ -973,10 +1011,10 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
       __syncthreads();
       return s_base;
     };
-    lb_finish(compact_row<PACK16>(n_words, count2, T.out_cols, T.out_cnt, wave_sum, base_of, (uint64_t)T.out_cap));
+    lb_finish(compact_row<PACK16>((uint32_t)n_words, count2, T.out_cols, T.out_cnt, wave_sum, base_of, (uint64_t)T.out_cap));
     return;
   }
-  uint32_t nnz = compact_row<PACK16>(n_words, count2, T.stage_cols + slot * T.row_cap, T.stage_cnt + slot * T.row_cap,
+  uint32_t nnz = compact_row<PACK16>((uint32_t)n_words, count2, T.stage_cols + slot * T.row_cap, T.stage_cnt + slot * T.row_cap,
                                      wave_sum);
   if (tid == 0) {
     T.row_nnz[slot] = nnz;
