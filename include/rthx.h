@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define RTHX_ABI_VERSION 3  /* 3: rthx_result_info.superseded / superseded_faults */
+#define RTHX_ABI_VERSION 4  /* 4: rthx_solve_spectral, rthx_spectral_apply, rthx_spectral_fractions */
 
 /* status codes */
 #define RTHX_OK 0
@@ -413,6 +413,73 @@ int rthx_solve_grey(const int64_t* row_ptr, const int32_t* cols, const double* v
 int rthx_solve_grey_smoothed(const rthx_smooth_result* F, const double* coeff, const double* h,
                              const rthx_solve_args* args, double* j_out, double* g_out,
                              rthx_solve_info* info);
+
+/* ------------------------------------------------------------------------
+ * Spectral GERT solve (equilibriumSpectral2D!, equilibriumSurfacesSpectral3D!;
+ * DESIGN.md §7f).  n elements, K = n_bands bands; vectors of length K n are
+ * band-major (x[k n + i]).  With g_k = F_k' j_k, b the reflected / scattered
+ * share (1 - eps, omega), prop the emitting property (eps, kappa), size the
+ * area or 4 V, w_k(T) the Planck band fractions and
+ * f_ik = prop_ik w_k(T_i) / sum_l prop_il w_l(T_i), the converged state is
+ *     j_k - b_k .* g_k = e .* f_k(T)                        every band
+ *     e_i = size_i sigma T_i^4 sum_k prop_ik w_k(T_i)       every element
+ *     e_i = q_i + sum_k (1 - b_ik) g_ik                     T_in[i] <= -0.1
+ * with T_i = T_in[i] where T_in[i] > -0.1.  Outer loop on the fractions f;
+ * per iteration one square system in the stacked j,
+ *     (A j)_ik = j_ik - b_ik g_ik - [T_in[i] <= -0.1] f_ik sum_l (1 - b_il) g_il,
+ * solved by the restarted GMRES of rthx_solve_grey, warm-started from the
+ * previous iterate.  One shared F (n_matrices = 1) serves every band, or one
+ * F per band (n_matrices = n_bands).
+ * ------------------------------------------------------------------------ */
+typedef struct rthx_spectral_band { /* one F_k; exactly one form is non-NULL */
+  const int64_t* row_ptr;           /* host CSR of F: row_ptr[n+1], cols, vals */
+  const int32_t* cols;
+  const double* vals;
+  const double* dense;                /* host dense, row-major n*n */
+  const rthx_smooth_result* smoothed; /* dense, already on the device */
+} rthx_spectral_band;
+
+typedef struct rthx_spectral_args {
+  int32_t device;
+  int32_t memory;         /* GMRES as rthx_solve_args */
+  int32_t itmax;
+  int32_t max_outer;      /* outer iteration cap (reference: 1000) */
+  double rtol;
+  double atol;
+  double convergence_tol; /* on ||j - j_prev|| / ||j|| (reference: 1e-12) */
+} rthx_spectral_args;
+
+typedef struct rthx_spectral_info {
+  int64_t n;
+  int32_t n_bands;
+  int32_t outer_iterations;
+  int32_t gmres_iterations; /* Arnoldi steps summed over the outer iterations */
+  int32_t converged;
+  double change;            /* last ||j - j_prev|| / ||j|| */
+  double residual;          /* true residual of the last linear solve */
+  double tolerance;         /* atol + rtol ||rhs|| of the last linear solve */
+  double ms_total;
+  double ms_apply;          /* HIP-event time summed over the banded applies */
+} rthx_spectral_info;
+
+/* band_limits[n_bands+1] (m, positive, increasing; the first band is taken
+ * from 0 and the last to infinity); b, prop [n_bands*n]; size, T_in, q_in [n].
+ * Outputs: j_out, g_out [n_bands*n]; T_out, e_out [n]. */
+int rthx_solve_spectral(const rthx_spectral_band* F, int32_t n_matrices, int64_t n, int32_t n_bands,
+                        const double* band_limits, const double* b, const double* prop, const double* size,
+                        const double* T_in, const double* q_in, const rthx_spectral_args* args, double* j_out,
+                        double* g_out, double* T_out, double* e_out, rthx_spectral_info* info);
+/* The banded operator alone: g_k = F_k' x_k into g_out[n_bands*n] and, when
+ * y_out is not NULL, y = A x (above) with the fractions f[n_bands*n] and the
+ * radiative-equilibrium flags is_radeq[n] (NULL: none). */
+int rthx_spectral_apply(const rthx_spectral_band* F, int32_t n_matrices, int64_t n, int32_t n_bands,
+                        int32_t device, const double* x, const double* b, const double* f,
+                        const uint8_t* is_radeq, double* g_out, double* y_out);
+/* The Planck kernel alone (emitFracBlackBodySpectrum, getBinsEmissionFractions,
+ * getWeightedEmissionFractions): band-major plain_out[n_bands*n] and, when not
+ * NULL, weighted_out[n_bands*n] with prop[n_bands*n] (NULL: prop = 1). */
+int rthx_spectral_fractions(const double* band_limits, int32_t n_bands, const double* T, const double* prop,
+                            int64_t n, int32_t device, double* plain_out, double* weighted_out);
 
 /* ------------------------------------------------------------------------
  * method=:direct: energy-partition Monte Carlo of one

@@ -33,45 +33,64 @@ namespace {
     if (_rc != RTHX_OK) return _rc; \
   } while (0)
 
-struct Solver {
-  hipStream_t s = nullptr;
-  int64_t n = 0;
+struct Solver : rthx::gs::Krylov {
   rthx::gs::Op op;
-  DevBuf c, h, x, r, w, V, small, part;
-  double* d(DevBuf& b) { return b.as<double>(); }
+  DevBuf c, part;
 };
 
-int d2h(Solver& S, double* dst, const double* src, size_t count) {
-  HIP_TRY(hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToHost, S.s), "hipMemcpy");
-  HIP_TRY(hipStreamSynchronize(S.s), "hipStreamSynchronize");
+}  // namespace
+
+namespace rthx {
+namespace gs {
+
+int Krylov::reserve(int memory) {
+  const int m = std::max(1, memory);
+  HIP_TRY(h.reserve(n * 8), "hipMalloc");
+  HIP_TRY(x.reserve(n * 8), "hipMalloc");
+  HIP_TRY(r.reserve(n * 8), "hipMalloc");
+  HIP_TRY(w.reserve(n * 8), "hipMalloc");
+  HIP_TRY(V.reserve((size_t)(m + 1) * n * 8), "hipMalloc Krylov basis");
+  HIP_TRY(small.reserve((size_t)(2 * (m + 1) + 1) * 8), "hipMalloc");
   return RTHX_OK;
 }
 
-int norm(Solver& S, const double* v, double* out) {
-  HIP_TRY(rthx::gs::multidot(v, v, 1, S.n, S.d(S.small), S.s), "multidot");
+int Krylov::d2h(double* dst, const double* src, size_t count) {
+  HIP_TRY(hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToHost, s), "hipMemcpy");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return RTHX_OK;
+}
+
+int Krylov::norm(const double* v, double* out) {
+  HIP_TRY(multidot(v, v, 1, n, small.as<double>(), s), "multidot");
   double t;
-  STRY(d2h(S, &t, S.d(S.small), 1));
+  STRY(d2h(&t, small.as<double>(), 1));
   *out = std::sqrt(t);
   return RTHX_OK;
 }
 
-int gmres(Solver& S, const rthx_solve_args& a, rthx_solve_info& info) {
-  using namespace rthx::gs;
+int gmres(Krylov& S, const Apply& A, const rthx_solve_args& a, bool warm, rthx_solve_info& info) {
   const int64_t n = S.n;
   const int m = std::max(1, a.memory);
   const int64_t itmax = a.itmax > 0 ? a.itmax : 2 * n;
   hipStream_t s = S.s;
-  double* x = S.d(S.x);
-  double* r = S.d(S.r);
-  double* w = S.d(S.w);
-  double* V = S.d(S.V);
-  double* sm = S.d(S.small);  // [2(m+1) + 1]: h1, h2, |w|^2
-  HIP_TRY(hipMemsetAsync(x, 0, n * 8, s), "hipMemset");
+  double* x = S.x.as<double>();
+  double* r = S.r.as<double>();
+  double* w = S.w.as<double>();
+  double* V = S.V.as<double>();
+  double* h = S.h.as<double>();
+  double* sm = S.small.as<double>();  // [2(m+1) + 1]: h1, h2, |w|^2
   double hnorm;
-  STRY(norm(S, S.d(S.h), &hnorm));
+  STRY(S.norm(h, &hnorm));
   const double tol = a.atol + a.rtol * hnorm;
-  HIP_TRY(hipMemcpyAsync(r, S.d(S.h), n * 8, hipMemcpyDeviceToDevice, s), "hipMemcpy");
   double beta = hnorm;
+  if (warm) {  // r = h - M x0
+    HIP_TRY(A(x, w), "apply");
+    HIP_TRY(sub(h, w, n, r, s), "sub");
+    STRY(S.norm(r, &beta));
+  } else {
+    HIP_TRY(hipMemsetAsync(x, 0, n * 8, s), "hipMemset");
+    HIP_TRY(hipMemcpyAsync(r, h, n * 8, hipMemcpyDeviceToDevice, s), "hipMemcpy");
+  }
   int64_t iters = 0;
   int cycles = 0;
   std::vector<double> H((size_t)(m + 1) * m), cs(m), sn(m), g(m + 1), y(m), hh(2 * (m + 1) + 1);
@@ -84,13 +103,13 @@ int gmres(Solver& S, const rthx_solve_args& a, rthx_solve_info& info) {
     int k = 0;
     while (k < m && iters < itmax) {
       double* vk = V + (int64_t)k * n;
-      HIP_TRY(apply(S.op, vk, S.d(S.c), w, s), "apply");
+      HIP_TRY(A(vk, w), "apply");
       HIP_TRY(multidot(V, w, k + 1, n, sm, s), "multidot");
       HIP_TRY(combine(V, sm, k + 1, -1.0, n, w, s), "combine");
       HIP_TRY(multidot(V, w, k + 1, n, sm + (m + 1), s), "multidot");
       HIP_TRY(combine(V, sm + (m + 1), k + 1, -1.0, n, w, s), "combine");
       HIP_TRY(multidot(w, w, 1, n, sm + 2 * (m + 1), s), "multidot");
-      STRY(d2h(S, hh.data(), sm, 2 * (m + 1) + 1));
+      STRY(S.d2h(hh.data(), sm, 2 * (m + 1) + 1));
       for (int i = 0; i <= k; ++i) Hat(i, k) = hh[i] + hh[(m + 1) + i];
       const double hn = std::sqrt(hh[2 * (m + 1)]);
       Hat(k + 1, k) = hn;
@@ -118,9 +137,9 @@ int gmres(Solver& S, const rthx_solve_args& a, rthx_solve_info& info) {
     }
     HIP_TRY(hipMemcpyAsync(sm, y.data(), k * 8, hipMemcpyHostToDevice, s), "hipMemcpy");
     HIP_TRY(combine(V, sm, k, 1.0, n, x, s), "combine");
-    HIP_TRY(apply(S.op, x, S.d(S.c), w, s), "apply");  // true residual h - M x
-    HIP_TRY(sub(S.d(S.h), w, n, r, s), "sub");
-    STRY(norm(S, r, &beta));
+    HIP_TRY(A(x, w), "apply");  // true residual h - M x
+    HIP_TRY(sub(h, w, n, r, s), "sub");
+    STRY(S.norm(r, &beta));
   }
   info.iterations = (int32_t)iters;
   info.cycles = cycles;
@@ -130,26 +149,54 @@ int gmres(Solver& S, const rthx_solve_args& a, rthx_solve_info& info) {
   return RTHX_OK;
 }
 
+// F' as CSR: counting sort by column (rows visited in order: columns of F' ascend)
+int csr_transpose(const int64_t* row_ptr, const int32_t* cols, const double* vals, int64_t n,
+                  std::vector<int64_t>& rp, std::vector<int32_t>& ci, std::vector<double>& v) {
+  if (!row_ptr || row_ptr[0] != 0) return fail(RTHX_EINVAL, "bad row_ptr");
+  const int64_t nnz = row_ptr[n];
+  if (nnz > 0 && (!cols || !vals)) return fail(RTHX_EINVAL, "null CSR arrays");
+  rp.assign(n + 1, 0);
+  for (int64_t i = 0; i < n; ++i) {
+    if (row_ptr[i + 1] < row_ptr[i]) return fail(RTHX_EINVAL, "row_ptr not monotone");
+    for (int64_t k = row_ptr[i]; k < row_ptr[i + 1]; ++k) {
+      if (cols[k] < 0 || cols[k] >= n || !std::isfinite(vals[k])) return fail(RTHX_EINVAL, "bad CSR entry");
+      rp[cols[k] + 1]++;
+    }
+  }
+  for (int64_t i = 0; i < n; ++i) rp[i + 1] += rp[i];
+  ci.assign(std::max<int64_t>(nnz, 1), 0);
+  v.assign(std::max<int64_t>(nnz, 1), 0.0);
+  std::vector<int64_t> pos(rp.begin(), rp.end() - 1);
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t k = row_ptr[i]; k < row_ptr[i + 1]; ++k) {
+      const int64_t q = pos[cols[k]]++;
+      ci[q] = (int32_t)i;
+      v[q] = vals[k];
+    }
+  return RTHX_OK;
+}
+
+}  // namespace gs
+}  // namespace rthx
+
+namespace {
+
 // Solve with the operator already set up on S; writes j and g to the host.
 int run(Solver& S, const double* coeff, const double* h, const rthx_solve_args* args, double* j_out, double* g_out,
         rthx_solve_info* info, double t0) {
   const int64_t n = S.n;
-  const int m = std::max(1, args->memory);
   HIP_TRY(S.c.reserve(n * 8), "hipMalloc");
-  HIP_TRY(S.h.reserve(n * 8), "hipMalloc");
-  HIP_TRY(S.x.reserve(n * 8), "hipMalloc");
-  HIP_TRY(S.r.reserve(n * 8), "hipMalloc");
-  HIP_TRY(S.w.reserve(n * 8), "hipMalloc");
-  HIP_TRY(S.V.reserve((size_t)(m + 1) * n * 8), "hipMalloc Krylov basis");
-  HIP_TRY(S.small.reserve((size_t)(2 * (m + 1) + 1) * 8), "hipMalloc");
+  STRY(S.reserve(args->memory));
   HIP_TRY(hipMemcpyAsync(S.c.p, coeff, n * 8, hipMemcpyHostToDevice, S.s), "hipMemcpy");
   HIP_TRY(hipMemcpyAsync(S.h.p, h, n * 8, hipMemcpyHostToDevice, S.s), "hipMemcpy");
   rthx_solve_info I{};
   I.n = n;
-  STRY(gmres(S, *args, I));
-  HIP_TRY(rthx::gs::apply(S.op, S.d(S.x), nullptr, S.d(S.w), S.s), "apply");  // g = F' j
-  STRY(d2h(S, j_out, S.d(S.x), n));
-  STRY(d2h(S, g_out, S.d(S.w), n));
+  const double* c = S.c.as<double>();
+  const rthx::gs::Apply M = [&S, c](const double* x, double* out) { return rthx::gs::apply(S.op, x, c, out, S.s); };
+  STRY(rthx::gs::gmres(S, M, *args, false, I));
+  HIP_TRY(rthx::gs::apply(S.op, S.x.as<double>(), nullptr, S.w.as<double>(), S.s), "apply");  // g = F' j
+  STRY(S.d2h(j_out, S.x.as<double>(), n));
+  STRY(S.d2h(g_out, S.w.as<double>(), n));
   I.ms_total = now_ms() - t0;
   if (info) *info = I;
   return RTHX_OK;
@@ -192,28 +239,10 @@ RTHX_EXPORT int rthx_solve_grey(const int64_t* row_ptr, const int32_t* cols, con
     S.op.F = Fd.as<double>();
     S.op.part = S.part.as<double>();
   } else {
-    if (!row_ptr || row_ptr[0] != 0) return fail(RTHX_EINVAL, "bad row_ptr");
-    const int64_t nnz = row_ptr[n];
-    if (nnz > 0 && (!cols || !vals)) return fail(RTHX_EINVAL, "null CSR arrays");
-    // F' as CSR: counting sort by column (rows visited in order: columns of F' ascend)
-    std::vector<int64_t> rp(n + 1, 0);
-    for (int64_t i = 0; i < n; ++i) {
-      if (row_ptr[i + 1] < row_ptr[i]) return fail(RTHX_EINVAL, "row_ptr not monotone");
-      for (int64_t k = row_ptr[i]; k < row_ptr[i + 1]; ++k) {
-        if (cols[k] < 0 || cols[k] >= n || !std::isfinite(vals[k])) return fail(RTHX_EINVAL, "bad CSR entry");
-        rp[cols[k] + 1]++;
-      }
-    }
-    for (int64_t i = 0; i < n; ++i) rp[i + 1] += rp[i];
-    std::vector<int32_t> ci(std::max<int64_t>(nnz, 1));
-    std::vector<double> v(std::max<int64_t>(nnz, 1));
-    std::vector<int64_t> pos(rp.begin(), rp.end() - 1);
-    for (int64_t i = 0; i < n; ++i)
-      for (int64_t k = row_ptr[i]; k < row_ptr[i + 1]; ++k) {
-        const int64_t q = pos[cols[k]]++;
-        ci[q] = (int32_t)i;
-        v[q] = vals[k];
-      }
+    std::vector<int64_t> rp;
+    std::vector<int32_t> ci;
+    std::vector<double> v;
+    STRY(rthx::gs::csr_transpose(row_ptr, cols, vals, n, rp, ci, v));
     HIP_TRY(trp.reserve((n + 1) * 8), "hipMalloc");
     HIP_TRY(tci.reserve(ci.size() * 4), "hipMalloc");
     HIP_TRY(tv.reserve(v.size() * 8), "hipMalloc");

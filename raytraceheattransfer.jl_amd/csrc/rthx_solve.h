@@ -5,6 +5,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
+#include <vector>
+
+#include "rthx_common.h"
+
 namespace rthx {
 namespace gs {
 
@@ -27,6 +32,24 @@ hipError_t multidot(const double* V, const double* w, int m, int64_t n, double* 
 hipError_t combine(const double* V, const double* coef, int m, double sign, int64_t n, double* w, hipStream_t s);
 hipError_t scale(const double* a, double alpha, int64_t n, double* out, hipStream_t s);
 hipError_t sub(const double* a, const double* b, int64_t n, double* out, hipStream_t s);
+
+// Restarted GMRES (rthx_solve.cpp) on vectors of length n: the right-hand
+// side in h, the solution in x.  The operator is a callback out = M x on the
+// stream s; with warm = true the iteration starts from the x already there
+// (and takes no step when that x meets the tolerance), else from zero.
+struct Krylov {
+  hipStream_t s = nullptr;
+  int64_t n = 0;
+  DevBuf h, x, r, w, V, small;
+  int reserve(int memory);
+  int d2h(double* dst, const double* src, size_t count);  // copy and wait
+  int norm(const double* v, double* out);
+};
+using Apply = std::function<hipError_t(const double* x, double* out)>;
+int gmres(Krylov& S, const Apply& M, const rthx_solve_args& a, bool warm, rthx_solve_info& info);
+// Host CSR of F -> CSR of F' (validated: RTHX_EINVAL on a malformed matrix).
+int csr_transpose(const int64_t* row_ptr, const int32_t* cols, const double* vals, int64_t n,
+                  std::vector<int64_t>& rp, std::vector<int32_t>& ci, std::vector<double>& v);
 
 }  // namespace gs
 }  // namespace rthx

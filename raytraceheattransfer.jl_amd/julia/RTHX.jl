@@ -23,7 +23,7 @@ module RTHX
 
 using SparseArrays
 
-const RTHX_ABI_VERSION = Int32(3)
+const RTHX_ABI_VERSION = Int32(4)
 const RTHX_FLAG_FAITHFUL_SAMPLING = UInt32(0x1)
 
 const LIB = Ref{String}("")

@@ -97,6 +97,12 @@ def load(path: Optional[str] = None) -> C.CDLL:
                                     C.POINTER(abi.SolveArgs), dp, dp, C.POINTER(abi.SolveInfo)]
     lib.rthx_solve_grey_smoothed.argtypes = [C.c_void_p, dp, dp, C.POINTER(abi.SolveArgs), dp, dp,
                                              C.POINTER(abi.SolveInfo)]
+    pb = C.POINTER(abi.SpectralBand)
+    lib.rthx_solve_spectral.argtypes = [pb, C.c_int32, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, dp,
+                                        C.POINTER(abi.SpectralArgs), dp, dp, dp, dp, C.POINTER(abi.SpectralInfo)]
+    lib.rthx_spectral_apply.argtypes = [pb, C.c_int32, C.c_int64, C.c_int32, C.c_int32, dp, dp, dp,
+                                        C.POINTER(C.c_uint8), dp, dp]
+    lib.rthx_spectral_fractions.argtypes = [dp, C.c_int32, dp, dp, C.c_int64, C.c_int32, dp, dp]
     lib.rthx_trace_direct.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_uint8), C.POINTER(abi.DirectArgs),
                                       C.POINTER(C.c_uint64), C.POINTER(abi.DirectInfo)]
     lib.rthx_debug_alias.argtypes = [dp, C.c_int64, C.POINTER(C.c_uint64)]

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-RTHX_ABI_VERSION = 3
+RTHX_ABI_VERSION = 4
 
 RTHX_OK = 0
 RTHX_EINVAL = -1
@@ -172,6 +172,49 @@ class SolveInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class SpectralBand(C.Structure):
+    """rthx_spectral_band (include/rthx.h): one F_k, exactly one form set."""
+    _fields_ = [
+        ("row_ptr", _p_i64),
+        ("cols", _p_i32),
+        ("vals", _p_f64),
+        ("dense", _p_f64),
+        ("smoothed", C.c_void_p),
+    ]
+
+
+class SpectralArgs(C.Structure):
+    """rthx_spectral_args (include/rthx.h)."""
+    _fields_ = [
+        ("device", C.c_int32),
+        ("memory", C.c_int32),
+        ("itmax", C.c_int32),
+        ("max_outer", C.c_int32),
+        ("rtol", C.c_double),
+        ("atol", C.c_double),
+        ("convergence_tol", C.c_double),
+    ]
+
+
+class SpectralInfo(C.Structure):
+    """rthx_spectral_info (include/rthx.h)."""
+    _fields_ = [
+        ("n", C.c_int64),
+        ("n_bands", C.c_int32),
+        ("outer_iterations", C.c_int32),
+        ("gmres_iterations", C.c_int32),
+        ("converged", C.c_int32),
+        ("change", C.c_double),
+        ("residual", C.c_double),
+        ("tolerance", C.c_double),
+        ("ms_total", C.c_double),
+        ("ms_apply", C.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class DirectArgs(C.Structure):
     """rthx_direct_args (include/rthx.h)."""
     _fields_ = [
@@ -272,6 +315,9 @@ EXPORTED_SYMBOLS = (
     "rthx_smooth_destroy",
     "rthx_solve_grey",
     "rthx_solve_grey_smoothed",
+    "rthx_solve_spectral",
+    "rthx_spectral_apply",
+    "rthx_spectral_fractions",
     "rthx_trace_direct",
     "rthx_view_factors_3d",
     "rthx_scene3d_create",

@@ -1,4 +1,4 @@
-"""Grey GERT solve on the MI355X.
+"""Grey and spectral GERT solves on the MI355X.
 
 Host mirror of equilibriumGrey2D! (src/HeatTransfer/equilibrium/
 equilibriumGrey2D.jl:80-211) with populateWorkspace!
@@ -6,7 +6,9 @@ equilibriumGrey2D.jl:80-211) with populateWorkspace!
 (writeResults/writeResultsToDomain3D.jl:112-144).  The linear system
 (I - Diagonal(coeff) F') j = h and g = F' j run in librthx (rthx_solve_grey*,
 restarted GMRES on the device); element bookkeeping stays on the host as in
-the reference.  No CPU fallback.
+the reference.  Spectral domains: equilibrium_spectral and
+equilibrium_surfaces_spectral_3d (rthx_solve_spectral: the outer loop on the
+emission fractions runs in librthx too).  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -196,17 +198,23 @@ def _write_results(dom, T, j, Abs, r):
             face.i_g = j[i] / (4 * math.pi * face.volume)
 
 
-def solve_equilibrium(dom, F=None, device: int = 0, verbose: bool = False):
-    """solveEquilibrium! (solveEquilibrium.jl:1-26) for grey 2D domains and grey
-    3D surface enclosures; F defaults to dom.F_smooth.  Spectral modes
-    (equilibriumSpectral2D!, equilibriumSurfacesSpectral3D!) are not part of
-    this package."""
+def solve_equilibrium(dom, F=None, device: int = 0, verbose: bool = False, max_iters: int = 1000,
+                      convergence_tol: float = 1e-12):
+    """solveEquilibrium! (solveEquilibrium.jl:1-26); F defaults to dom.F_smooth.
+    Grey 2D domains and grey 3D surface enclosures take the grey solve (which
+    ignores max_iters and convergence_tol, as the reference's does); spectral
+    domains take the spectral solve."""
     from .domain3d import ViewFactorDomain3D
 
-    if dom.spectral_mode != "grey":
-        raise NotImplementedError("spectral GERT solves (equilibriumSpectral2D!, ...Spectral3D!) are out of scope")
     if isinstance(dom, ViewFactorDomain3D):  # solveEquilibrium.jl:13-22
-        return equilibrium_surfaces_grey_3d(dom, dom.F_smooth if F is None else F, device=device, verbose=verbose)
+        F3 = dom.F_smooth if F is None else F
+        if dom.spectral_mode != "grey":
+            return equilibrium_surfaces_spectral_3d(dom, F3, device=device, max_iters=max_iters,
+                                                    convergence_tol=convergence_tol, verbose=verbose)
+        return equilibrium_surfaces_grey_3d(dom, F3, device=device, verbose=verbose)
+    if dom.spectral_mode != "grey":
+        return equilibrium_spectral(dom, F, device=device, max_iters=max_iters, convergence_tol=convergence_tol,
+                                    verbose=verbose)
     return equilibrium_grey(dom, F, device=device, verbose=verbose)
 
 
@@ -253,4 +261,207 @@ def equilibrium_surfaces_grey_3d(domain, F, spectral_bin: int = 1, device: int =
             s.T_w = s.T_in_w
             s.q_w = e - Abs[i]
     domain.energy_error = float(np.sum(j - r - Abs))
+    return T, j, Abs, r
+
+
+# --------------------------------------------------------------------------
+# spectral GERT solve
+# --------------------------------------------------------------------------
+def _check_band_limits(limits, n_bins: int) -> np.ndarray:
+    """The checks of equilibriumSpectral2D! (equilibriumSpectral2D.jl:58-79)."""
+    if limits is None:
+        raise ValueError("Spectral solve requires wavelength band limits to be set (dom.wavelength_band_limits)")
+    lim = np.ascontiguousarray(limits, dtype=np.float64)
+    if lim.ndim != 1 or len(lim) < 4:
+        raise ValueError("wavelength_band_limits must have at least 4 values (defining 3 bins)")
+    if np.any(lim <= 0):
+        raise ValueError("wavelength_band_limits must all be positive (wavelengths > 0)")
+    if np.any(np.diff(lim) <= 0):
+        raise ValueError("wavelength_band_limits must be strictly increasing (no duplicates)")
+    if len(lim) != n_bins + 1:
+        raise ValueError(f"{len(lim)} wavelength_band_limits for {n_bins} spectral bins (n_bins + 1 expected)")
+    return lim
+
+
+def _band_struct(F, n: int, handle, keep: list) -> abi.SpectralBand:
+    """One rthx_spectral_band from a SmoothHandle, a scipy sparse matrix or a
+    dense array (its leading n x n block); `keep` holds the arrays alive."""
+    band = abi.SpectralBand()
+    if handle is not None:
+        band.smoothed = handle.handle
+        keep.append(handle)
+    elif sp.issparse(F):
+        Fc = F.tocsr()[:n, :n]
+        rp = np.ascontiguousarray(Fc.indptr, dtype=np.int64)
+        ci = np.ascontiguousarray(Fc.indices, dtype=np.int32)
+        vv = np.ascontiguousarray(Fc.data, dtype=np.float64)
+        keep += [rp, ci, vv]
+        band.row_ptr, band.cols, band.vals = abi.ptr(rp, C.c_int64), abi.ptr(ci, C.c_int32), abi.ptr(vv, C.c_double)
+    else:
+        Fd = np.ascontiguousarray(np.asarray(F)[:n, :n], dtype=np.float64)
+        keep.append(Fd)
+        band.dense = abi.ptr(Fd, C.c_double)
+    return band
+
+
+def solve_spectral(F, limits, b, prop, size, T_in, q_in, device: int = 0, max_iters: int = 1000,
+                   convergence_tol: float = 1e-12, handles=None, rtol: float = 1e-12,
+                   atol: float = math.sqrt(np.finfo(np.float64).eps), memory: int = 50):
+    """rthx_solve_spectral.  F: one matrix (shared by every band) or a list of
+    K, each dense, scipy sparse, or None with a SmoothHandle in `handles` at
+    that place; b, prop: [K, n]; size, T_in, q_in: [n].  Returns
+    (j[K, n], g[K, n], T[n], e[n], info)."""
+    lib = load()
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    prop = np.ascontiguousarray(prop, dtype=np.float64)
+    K, n = b.shape
+    mats = list(F) if isinstance(F, (list, tuple)) else [F]
+    hs = list(handles) if handles is not None else [None] * len(mats)
+    if len(mats) > 1 and all(m is mats[0] for m in mats) and all(h is hs[0] for h in hs):
+        mats, hs = mats[:1], hs[:1]  # grouped bins share one matrix: one pass over it
+    keep: list = []
+    bands = (abi.SpectralBand * len(mats))(*[_band_struct(m, n, h, keep) for m, h in zip(mats, hs)])
+    lim = np.ascontiguousarray(limits, dtype=np.float64)
+    size = np.ascontiguousarray(size, dtype=np.float64)
+    T_in = np.ascontiguousarray(T_in, dtype=np.float64)
+    q_in = np.ascontiguousarray(q_in, dtype=np.float64)
+    a = abi.SpectralArgs()
+    a.device, a.memory, a.itmax, a.max_outer = device, memory, 0, int(max_iters)
+    a.rtol, a.atol, a.convergence_tol = rtol, atol, convergence_tol
+    j = np.empty((K, n))
+    g = np.empty((K, n))
+    T = np.empty(n)
+    e = np.empty(n)
+    inf = abi.SpectralInfo()
+    dp = C.c_double
+    check(lib.rthx_solve_spectral(bands, len(mats), n, K, abi.ptr(lim, dp), abi.ptr(b, dp), abi.ptr(prop, dp),
+                                  abi.ptr(size, dp), abi.ptr(T_in, dp), abi.ptr(q_in, dp), C.byref(a),
+                                  abi.ptr(j, dp), abi.ptr(g, dp), abi.ptr(T, dp), abi.ptr(e, dp), C.byref(inf)))
+    del keep
+    return j, g, T, e, inf.as_dict()
+
+
+def _report(si: dict, info: Optional[dict], verbose: bool) -> None:
+    if info is not None:
+        info.update(si)
+    if verbose:
+        print(f"spectral solve: {si['outer_iterations']} outer iterations, {si['gmres_iterations']} GMRES steps, "
+              f"change {si['change']:.3e}, residual {si['residual']:.3e} (tolerance {si['tolerance']:.3e})")
+    if not si["converged"]:
+        import warnings
+
+        warnings.warn(f"spectral solve not converged after {si['outer_iterations']} outer iterations "
+                      f"(change {si['change']:.3e})")
+
+
+def equilibrium_spectral(dom, F=None, device: int = 0, max_iters: int = 1000, convergence_tol: float = 1e-12,
+                         verbose: bool = False, info: Optional[dict] = None):
+    """equilibriumSpectral2D! (equilibriumSpectral2D.jl) for both spectral
+    modes, solved on the device (rthx_solve_spectral).  F: one
+    matrix or a list of one per band (default dom.F_smooth, read in place on
+    the device when it lives there).  Writes per band j, g_a, e, r, g (and i)
+    into the per-bin vectors of every face (writeResultsToDomainSpectralBin!),
+    T and q (writeTemperaturesHeatSources!) and dom.energy_error (one value
+    per band); returns (T, j[K, n], Abs[K, n], r[K, n])."""
+    from .direct import _ensure_result_fields
+
+    K = dom.n_spectral_bins
+    lim = _check_band_limits(dom.wavelength_band_limits, K)
+    wss = [populate_workspace(dom, k) for k in range(1, K + 1)]
+    ns, nv = len(wss[0]["Area"]), len(wss[0]["Volume"])
+    n = ns + nv
+    b = np.array([np.concatenate([1.0 - ws["epsw"], ws["omega_g"]]) for ws in wss])
+    prop = np.array([np.concatenate([ws["epsw"], ws["kappa_g"]]) for ws in wss])
+    size = np.concatenate([wss[0]["Area"], 4.0 * wss[0]["Volume"]])
+    T_in = np.concatenate([wss[0]["Tw"], wss[0]["Tg"]])
+    q_in = np.concatenate([wss[0]["qw"], wss[0]["qg"]])
+    handles = None
+    if F is None:
+        if dom.F_smooth_device() is not None:
+            handles = [dom.F_smooth_device()]
+        else:
+            F = dom.F_smooth
+    else:
+        dev = getattr(dom, "_F_smooth_device", None)
+        if dev is not None and dev[0] is F and dev[1].dense:
+            handles = [dev[1]]
+    if handles is not None:
+        F = [None]
+    j, g, T, e, si = solve_spectral(F, lim, b, prop, size, T_in, q_in, device=device, max_iters=max_iters,
+                                    convergence_tol=convergence_tol, handles=handles)
+    _report(si, info, verbose)
+    r = b * g
+    Abs = (1.0 - b) * g
+    em = np.maximum(j - r, 0.0)
+    _ensure_result_fields(dom)
+    for (c, f, w), s in dom.surface_mapping.items():  # writeResultsToDomainSpectralBin!
+        face = dom.fine_mesh[c - 1][f - 1]
+        i, k = s - 1, w - 1
+        if not isinstance(getattr(face, "i_w", None), list) or len(face.i_w) != len(face.solidWalls):
+            face.i_w = [0.0] * len(face.solidWalls)
+        face.j_w[k] = j[:, i].copy()
+        face.g_a_w[k] = Abs[:, i].copy()
+        face.e_w[k] = em[:, i].copy()
+        face.r_w[k] = r[:, i].copy()
+        face.g_w[k] = Abs[:, i] + r[:, i]
+        face.i_w[k] = j[:, i] / (math.pi * face.area[k])
+        if face.T_in_w[k] > -0.1:  # writeTemperaturesHeatSources!
+            face.T_w[k] = face.T_in_w[k]
+            face.q_w[k] = float(np.sum(em[:, i]) - np.sum(Abs[:, i]))
+        else:
+            face.T_w[k] = T[i]
+            face.q_w[k] = face.q_in_w[k]
+    if nv:
+        for (c, f), v in dom.volume_mapping.items():
+            face = dom.fine_mesh[c - 1][f - 1]
+            i = ns + v - 1
+            face.j_g = j[:, i].copy()
+            face.g_a_g = Abs[:, i].copy()
+            face.e_g = em[:, i].copy()
+            face.r_g = r[:, i].copy()
+            face.g_g = Abs[:, i] + r[:, i]
+            face.i_g = j[:, i] / (4 * math.pi * face.volume)
+            if face.T_in_g > -0.1:
+                face.T_g = face.T_in_g
+                face.q_g = float(np.sum(em[:, i]) - np.sum(Abs[:, i]))
+            else:
+                face.T_g = T[i]
+                face.q_g = face.q_in_g
+    dom.energy_error = [float(np.sum(j[k] - g[k])) for k in range(K)]  # sum((I - F_k') j_k)
+    return T, j, Abs, r
+
+
+def equilibrium_surfaces_spectral_3d(domain, F, device: int = 0, max_iters: int = 1000,
+                                     convergence_tol: float = 1e-12, verbose: bool = False,
+                                     info: Optional[dict] = None):
+    """equilibriumSurfacesSpectral3D! (equilibriumSurfacesSpectral3D.jl): the
+    spectral solve with one shared F, then writeResultsToDomainSpectralBin3D!
+    and writeTemperaturesHeatSources!.  Returns (T, j[K, n], Abs[K, n], r[K, n])."""
+    K = domain.n_spectral_bins
+    lim = _check_band_limits(domain.wavelength_band_limits, K)
+    subs = domain.subfaces()
+    n = len(subs)
+    eps = np.array([np.broadcast_to(np.asarray(s.epsilon, dtype=np.float64), (K,)) for s in subs]).T.copy()
+    area = np.array([s.area for s in subs])
+    T_in = np.array([s.T_in_w for s in subs])
+    q_in = np.array([s.q_in_w for s in subs])
+    Fm = F if sp.issparse(F) else np.asarray(F)[:n, :n]
+    j, g, T, e, si = solve_spectral(Fm, lim, 1.0 - eps, eps, area, T_in, q_in, device=device, max_iters=max_iters,
+                                    convergence_tol=convergence_tol)
+    _report(si, info, verbose)
+    b = 1.0 - eps
+    r = b * g
+    Abs = (1.0 - b) * g
+    em = np.maximum(j - r, 0.0)
+    for i, s in enumerate(subs):
+        s.j_w, s.g_a_w, s.e_w, s.r_w = j[:, i].copy(), Abs[:, i].copy(), em[:, i].copy(), r[:, i].copy()
+        s.g_w = Abs[:, i] + r[:, i]
+        s.i_w = j[:, i] / (math.pi * s.area)
+        if s.T_in_w > -0.1:
+            s.T_w = s.T_in_w
+            s.q_w = float(np.sum(em[:, i]) - np.sum(Abs[:, i]))
+        else:
+            s.T_w = T[i]
+            s.q_w = s.q_in_w
+    domain.energy_error = [float(np.sum(j[k] - g[k])) for k in range(K)]
     return T, j, Abs, r
