@@ -576,7 +576,7 @@ RTHX_EXPORT int rthx_domain_create(const rthx_domain_desc* desc, int32_t device,
     std::sort(ys.begin(), ys.end());
     ys.erase(std::unique(ys.begin(), ys.end()), ys.end());
     const int64_t lnx = (int64_t)xs.size() - 1, lny = (int64_t)ys.size() - 1;
-    bool ok = lnx >= 1 && lny >= 1 && lnx * lny == (int64_t)nf && lnx <= 4096 && lny <= 4096;
+    bool ok = lnx >= 1 && lny >= 1 && lnx * lny == (int64_t)nf && lnx <= rthx::kLatMaxDim && lny <= rthx::kLatMaxDim;  // (lat_cell: 24-bit products)
     std::vector<int32_t> map(ok ? (size_t)(lnx * lny) : 0, -1);
     bool identity = ok;
     for (size_t f = 0; f < nf && ok; ++f) {

@@ -85,6 +85,7 @@ struct CoarseLayout {
 // walls' surface indices come from f_surf).  Fine cell (i, j) is polygon
 // j nx + i when `identity`, else lat_map[j nx + i].  bytes == 0: not a
 // lattice.
+constexpr int kLatMaxDim = 4096;  // most boxes a side (host: no lattice beyond it); cell indices then fit 24-bit multiplies
 struct LatticeLayout {
   int32_t bytes;             // blob bytes (multiple of 16)
   int32_t nx, ny;
@@ -364,7 +365,8 @@ __host__ __device__ __forceinline__ double neg_log_u32(uint32_t w, const double*
   const int i = (int)((tmp >> 45) & (kLogTable - 1));
   const int32_t k = ((int32_t)(uint32_t)(tmp >> 32) >> 20) - 32;
   const double z = bitsd(ix - (tmp & 0xFFF0000000000000ull));
-  const double invc = tab[4 * i], t_hi = tab[4 * i + 1], t_lo = tab[4 * i + 2];
+  const double* const te = (const double*)((const char*)tab + ((uint32_t)i << 5));  // (a 32-bit byte offset on the base)
+  const double invc = te[0], t_hi = te[1], t_lo = te[2];
   const double r = __builtin_fma(z, invc, -1.0);
   double q = __builtin_fma(r, 1.0 / 7.0, -1.0 / 6.0);
   q = __builtin_fma(r, q, sconst(1.0 / 5.0));
@@ -429,7 +431,11 @@ __device__ __forceinline__ double cos_2pi_u32(uint32_t w, const double* tab) {
   const double cd = __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, -1.0 / 720.0, 1.0 / 24.0), -0.5), 1.0);
   const double ps = __builtin_fma(z, __builtin_fma(z, -1.0 / 5040.0, 1.0 / 120.0), sconst(-1.0 / 6.0));
   const double sd = __builtin_fma(d * z, ps, d);
-  const double C = tab[2 * j], S = tab[2 * j + 1];
+  // the (cos, sin) pair in one 16-byte load; 8-byte aligned only, because a
+  // bin's table block is an odd number of doubles (kLdsTableDoubles)
+  typedef double pair_t __attribute__((ext_vector_type(2), aligned(8)));
+  const pair_t cs = *(const pair_t*)((const char*)tab + ((uint32_t)j << 4));  // (a 32-bit byte offset on the base)
+  const double C = cs.x, S = cs.y;
   return __builtin_fma(C, cd, -(S * sd));
 }
 
@@ -1004,13 +1010,33 @@ __device__ __forceinline__ int lattice_index(const double RTHX_LDS* b, int n, do
   // negative guess clamps to 0 either way
   int i;
   __asm__("v_cvt_i32_f64 %0, %1" : "=v"(i) : "v"(__dmul_rn(x - b[0], inv)));
-  i = __builtin_elementwise_min(__builtin_elementwise_max(i, 0), n - 1);  // (v_med3_i32)
+  // n >= 1, so min(max(i, 0), n - 1) is the median of (i, 0, n - 1): one
+  // v_med3_i32, written out because the compiler cannot see 0 <= n - 1 and
+  // emits v_max_i32 + v_min_i32.  n is wave-uniform at every caller (a
+  // layout field or a literal): the scalar operand (readfirstlane folds away
+  // where the compiler holds n - 1 in a scalar register already).
+  __asm__("v_med3_i32 %0, %1, 0, %2" : "=v"(i) : "v"(i), "s"(__builtin_amdgcn_readfirstlane(n - 1)));
   // both bounds in one paired read, tested without a branch
   const double lo = b[i], hi = b[i + 1];
   if ((lo <= x) & (x < hi)) return i;
   while (i > 0 && x < b[i]) --i;
   while (i < n - 1 && !(x < b[i + 1])) ++i;
   return (b[i] <= x && x < b[i + 1]) ? i : -1;
+}
+
+// Cell j nx + i of a LatticeLayout: j < ny and nx are at most kLatMaxDim, so
+// the product is a 24-bit multiply-add (v_mad_u32_u24) where the 32-bit one
+// compiled to the 64-bit v_mad_u64_u32.
+static_assert(kLatMaxDim <= (1 << 12), "j nx + i must fit the 24-bit multiply and its 32-bit byte offsets");
+__device__ __forceinline__ int lat_cell(int i, int j, int nx) {
+  return (int)(__umul24((uint32_t)j, (uint32_t)nx) + (uint32_t)i);
+}
+
+// base[byte_off / sizeof(T)] for a 32-bit byte offset: the load takes the
+// scalar base and one offset register (no 64-bit address arithmetic).
+template <class T>
+__device__ __forceinline__ T ld_off32(const T RTHX_GLOBAL* base, uint32_t byte_off) {
+  return *(const T RTHX_GLOBAL*)((const char RTHX_GLOBAL*)base + byte_off);
 }
 
 struct LatticeLds {
@@ -1056,7 +1082,7 @@ __device__ __forceinline__ int segment_lat(const DevDomain& D, const TraceParams
   } else {
     const int i0 = lattice_index(L.xs, G.nx, G.inv_x, px), j0 = lattice_index(L.ys, G.ny, G.inv_y, py);
     if (i0 < 0 || j0 < 0) return -1;
-    const int f0 = G.identity ? j0 * G.nx + i0 : D.lat_map[j0 * G.nx + i0];
+    const int f0 = G.identity ? lat_cell(i0, j0, G.nx) : D.lat_map[lat_cell(i0, j0, G.nx)];
     beta = D.beta[(size_t)P.bin * D.n_fine + f0];
     tau_b = __dmul_rn(beta, u);
     gas = acc + tau_b >= S;
@@ -1068,7 +1094,8 @@ __device__ __forceinline__ int segment_lat(const DevDomain& D, const TraceParams
   py = py + __dmul_rn(t, dy);
   const int i = lattice_index(L.xs, G.nx, G.inv_x, px), j = lattice_index(L.ys, G.ny, G.inv_y, py);
   if (i < 0 || j < 0) return -1;
-  if (gas) return D.n_surfaces + (G.identity ? j * G.nx + i : D.lat_map[j * G.nx + i]);
+  const int cell = lat_cell(i, j, G.nx);
+  if (gas) return D.n_surfaces + (G.identity ? cell : D.lat_map[cell]);
   // the end point lies in fine box (i, j) (half-open: lattice_index): the
   // wall is the nearer of the two the ray points to, in wall order, as the
   // four-wall test of dist_to_rect would find it (w = 0 when none qualifies,
@@ -1079,7 +1106,8 @@ __device__ __forceinline__ int segment_lat(const DevDomain& D, const TraceParams
   // same index as the boundary arrays the lattice blob held, without the
   // per-lane selects of array and edge; headline 0.7722 -> 0.7658 ms, D2
   // 19.92 -> 19.58 ms, profiles/round6/ab/lat_fsurf.log)
-  return D.f_surf[4 * (G.identity ? j * G.nx + i : D.lat_map[j * G.nx + i]) + w];
+  // (n_fine <= kLatMaxDim^2 = 2^24 cells of 16 bytes: a 32-bit byte offset)
+  return ld_off32(D.f_surf, ((uint32_t)(G.identity ? cell : D.lat_map[cell]) << 4) + ((uint32_t)w << 2));
 }
 
 // ---------------------------------------------------------------------------

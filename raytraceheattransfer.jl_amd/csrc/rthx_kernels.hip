@@ -50,8 +50,8 @@ namespace rthx {
 #endif
 constexpr int kBufferRsrcWord3 = 0x00020000;
 constexpr int kSc1 = 16;
-#ifndef RTHX_PW_ROTATE
-#define RTHX_PW_ROTATE 1  // SINGLE group rounds: free-path words by rotation (0: per-lane selects on r & 3)
+#ifndef RTHX_ROUND_UNROLL
+#define RTHX_ROUND_UNROLL 1  // SINGLE group rounds: the four rays of a round unrolled (0: one body, the word picked by k)
 #endif
 #ifndef RTHX_GTAB
 // 1: the cos / log tables (and 1 / beta_uniform) read from the domain's
@@ -555,9 +555,11 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
     // indices: a lane traces rays 4q .. 4q+3 of groups q = q0 + tid,
     // q0 + tid + nthr, ..., and one free-path Philox block (q, g, 1, bin)
     // serves all four (RayWords).  The groups left over after the last full
-    // round over the lanes are traced one ray per lane, each drawing its
-    // own free-path block, so that no lane traces more than one ray beyond
-    // the row's average.
+    // round over the lanes are one more round on the first lanes, so they
+    // share their blocks like every other group.  (One ray per lane for
+    // them, each drawing its own block, needs a second loop with its own
+    // code site for the ray; that form does not compile -- "illegal VGPR to
+    // SGPR copy" in the backend -- and was not measured.)
     auto one_ray = [&](uint32_t r, bool have_pw, uint32_t pw, auto ek) {
       constexpr int EK = decltype(ek)::value;
       double ox, oy, px, py;
@@ -573,54 +575,51 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
       tally(a);
       record(r, a, ox, oy, px, py);
     };
-    const uint32_t rb = (uint32_t)r_begin, re = (uint32_t)r_end;
+    const uint32_t rb = (uint32_t)r_begin;
+    const uint32_t re = (uint32_t)r_end > rb ? (uint32_t)r_end : rb;  // (a part that begins past the row's end is empty)
     const uint32_t q0 = rb >> 2, q1 = (re + 3u) >> 2;
-    const uint32_t q_full = q0 + ((q1 - q0) / (uint32_t)nthr) * (uint32_t)nthr;
+    const uint32_t nt = (uint32_t)__builtin_amdgcn_readfirstlane(nthr);
     // (workgroup-uniform flags, in scalar registers)
     const bool volume = __builtin_amdgcn_readfirstlane((int)lds_opaque(&s_emit)->surface) == 0;
     const bool vrect = volume && __builtin_amdgcn_readfirstlane((int)lds_opaque(&s_emit)->rect) != 0;
-    // Every lane runs the same number of group rounds (q_full - q0 is a
-    // multiple of nthr), then the tail rays one per lane: the iteration
-    // count and the phase are uniform over the workgroup (scalar registers),
-    // and a lane's ray index is tid plus a uniform offset.  One code site for
-    // the block and for the ray keeps the loop body single.
-    const uint32_t n_grp = 4u * ((q_full - q0) / (uint32_t)nthr);
-    const uint32_t r_tail = 4u * q_full > rb ? 4u * q_full : rb;
-    const uint32_t n_it = n_grp + (re > r_tail ? (re - r_tail + (uint32_t)nthr - 1u) / (uint32_t)nthr : 0u);
+    // The loop runs over group rounds: in round rd a lane holds group
+    // q = q0 + rd nthr + tid, draws its free-path block once and traces the
+    // group's four rays r = 4q + k with pw = word k, k uniform.  The round
+    // count is uniform over the workgroup; the last round may be partial
+    // (the lanes with q < q1).  Only the first round (rb not a
+    // multiple of four: a split part) and the round that holds group q1 - 1
+    // (re not a multiple of four) can hold rays outside [rb, re): that is a
+    // scalar test per round, and only those rounds mask their rays by range.
+    // (the quotient comes off the VALU: back into a scalar register, so that
+    // the round counter and the edge test stay scalar)
+    const uint32_t n_rd = (uint32_t)__builtin_amdgcn_readfirstlane((int)((q1 - q0 + nt - 1u) / nt));
     // The loop is compiled twice: for an axis-aligned rectangle volume
     // emitter (the cells of a lattice: the kind tests of the emission fold
     // away, EmitKind) and for any emitter.
     auto rounds = [&](auto ek) {
-    uint32_t b0 = 0u, b1 = 0u, b2 = 0u, b3 = 0u;
-    for (uint32_t it = 0; it < n_it; ++it) {
-      const bool grp = it < n_grp;
-      const uint32_t r = grp ? 4u * (q0 + (it >> 2) * (uint32_t)nthr + (uint32_t)tid) + (it & 3u)
-                             : r_tail + (it - n_grp) * (uint32_t)nthr + (uint32_t)tid;
-      if (volume && (!grp || (it & 3u) == 0u)) {
-        uint32_t b[4];
-        philox_words(r >> 2, (uint32_t)g, 1u, (uint32_t)P.bin, P.key0, P.key1, b);
-        b0 = b[0]; b1 = b[1]; b2 = b[2]; b3 = b[3];
-#if RTHX_PW_ROTATE
-        if (!grp) {
-          // (a tail ray's own block: word r & 3 by bit selects -- a compare
-          // chain becomes a branchy switch)
-          const uint32_t k = r & 3u;
-          b0 = (k & 2u) ? ((k & 1u) ? b3 : b2) : ((k & 1u) ? b1 : b0);
-        }
-#endif
-      }
-#if RTHX_PW_ROTATE
-      // the group rounds' rays take the block's words in order: b0, then the
-      // words move down (three moves instead of per-lane selects on r & 3)
-      const uint32_t pw = b0;
-      b0 = b1;
-      b1 = b2;
-      b2 = b3;
+    uint32_t q = q0 + (uint32_t)tid;
+    uint32_t q_lo = q0;  // (scalar) the round's first group
+    for (uint32_t rd = 0; rd < n_rd; ++rd, q += nt, q_lo += nt) {
+      if (q < q1) {  // (false only in a partial last round)
+        uint32_t b[4] = {0u, 0u, 0u, 0u};
+        if (volume) philox_words(q, (uint32_t)g, 1u, (uint32_t)P.bin, P.key0, P.key1, b);
+        const bool edge = (rd == 0u && (rb & 3u) != 0u) || (q_lo + nt >= q1 && (re & 3u) != 0u);
+#if RTHX_ROUND_UNROLL
+#pragma unroll
 #else
-      const uint32_t k = r & 3u;
-      const uint32_t pw = (k & 2u) ? ((k & 1u) ? b3 : b2) : ((k & 1u) ? b1 : b0);
+#pragma nounroll
 #endif
-      if (r >= rb && r < re) one_ray(r, true, pw, ek);
+        for (uint32_t k = 0; k < 4u; ++k) {
+          uint32_t r = 4u * q + k;
+          const uint32_t pw = k == 0u ? b[0] : k == 1u ? b[1] : k == 2u ? b[2] : b[3];
+          bool in = true;
+          if (edge) {
+            __asm__ volatile("" : "+v"(r));  // (keeps the range test inside the scalar branch)
+            in = r >= rb && r < re;
+          }
+          if (in) one_ray(r, true, pw, ek);
+        }
+      }
     }
     };
     if constexpr (!FAITHFUL) {
