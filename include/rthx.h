@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define RTHX_ABI_VERSION 4  /* 4: rthx_solve_spectral, rthx_spectral_apply, rthx_spectral_fractions */
+#define RTHX_ABI_VERSION 5  /* 5: rthx_trace_exchange_rays, rthx_result_accumulate[_csr], rthx_result_sampling_error */
 
 /* status codes */
 #define RTHX_OK 0
@@ -199,7 +199,56 @@ void rthx_result_destroy(rthx_result* res);
 int rthx_trace_exchange(rthx_domain* dom, const rthx_trace_args* args,
                         rthx_result* res);
 
+/* As rthx_trace_exchange, for ray ids [ray_begin, ray_begin + args->rays_per_emitter)
+ * of every selected emitter; ray_begin = 0 is rthx_trace_exchange exactly.  A
+ * ray is a pure function of (seed, bin, emitter, ray id), so tracing the
+ * ranges [0, a) and [a, b) and summing the counts with rthx_result_accumulate
+ * gives the counts of one trace of [0, b), bit for bit.  The argument checks
+ * of rthx_trace_exchange apply; ray_begin < 0 is RTHX_EINVAL, and
+ * ray_begin + rays_per_emitter >= 2^32 is RTHX_ERANGE: the kernels index rays
+ * in 32 bits.  rthx_result_info reports the rays of this call; with a
+ * recorder, the recorded rays are those of this range, in ray order. */
+int rthx_trace_exchange_rays(rthx_domain* dom, const rthx_trace_args* args, int64_t ray_begin,
+                             rthx_result* res);
+
 int rthx_result_get_info(const rthx_result* res, rthx_result_info* info);
+
+/* dst += src: counts summed entry by entry, rows stay column-ascending.  Both
+ * are single-device results on one device over the same rows: equal N,
+ * emitter_begin, emitter_stride and row count, else RTHX_EINVAL; a result of
+ * rthx_multi_trace_exchange is RTHX_EINVAL too.  A pending RTHX_FLAG_ASYNC
+ * trace in either is completed first.  The rays per emitter add up, and their
+ * sum must stay below 2^32, else RTHX_ERANGE: that bound keeps the 32-bit
+ * counts from overflowing.  Afterwards dst reads exactly like one trace of
+ * the summed rays: its info (rays_per_emitter, rays_traced, nnz, lost_total,
+ * and lost_max_row as the maximum over the rows of their summed losses) and
+ * every copy, device CSR and smoothing call.  trace_ms, pack_ms and the
+ * recorded rays of dst stay as they were.  The two ray sets must be disjoint
+ * -- different ray ranges of one seed, or different seeds -- for the sum to be
+ * a sample of that many rays; the library cannot check it, the caller
+ * must.  Results of rthx_trace_exchange_3d accumulate in the same way. */
+int rthx_result_accumulate(rthx_result* dst, const rthx_result* src);
+
+/* The same, with src given as a device CSR block in the layout that
+ * rthx_result_copy_csr_device writes: row_off[n_rows+1] from 0, cols, counts,
+ * all on dst's device, each row column-ascending, which traced
+ * rays_per_emitter rays per row.  n_rows must be dst's row count. */
+int rthx_result_accumulate_csr(rthx_result* dst, int64_t n_rows, const int64_t* row_off,
+                               const uint32_t* cols, const uint32_t* counts,
+                               int64_t rays_per_emitter);
+
+/* Device time in ms of the kernels of the last accumulate into res, measured
+ * with events; 0 before the first. */
+int rthx_result_accumulate_ms(const rthx_result* res, double* ms_out);
+
+/* Binomial sampling error of F_raw = count / tallied, from the counts on the
+ * device.  With p_ij = c_ij / n_i (n_i = rays row i tallied) and
+ * s_i = (1 - sum_j p_ij^2) / n_i, it returns
+ *   *rms_out     = sqrt(sum_i s_i / (rows_traced * N))
+ *   *max_row_out = max_i sqrt(s_i)
+ * Rows with n_i = 0 contribute 0.  Either pointer may be NULL.  A
+ * single-device result. */
+int rthx_result_sampling_error(const rthx_result* res, double* rms_out, double* max_row_out);
 
 /* Copy the count matrix as CSR over all N rows (rows that were not traced are
  * empty): row_ptr[N+1], cols[nnz], counts[nnz].  F_raw(i,j) of the reference

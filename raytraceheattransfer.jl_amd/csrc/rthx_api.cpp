@@ -897,6 +897,7 @@ int run_trace(rthx_domain* dom, const rthx_trace_args* a, const TracePlan& p, rt
 
   rthx::TraceParams P{};
   P.R = R;
+  P.ray_base = p.ray_base;
   P.g_begin = a->emitter_begin;
   P.g_stride = a->emitter_stride;
   P.eta = a->nudge;
@@ -1005,7 +1006,9 @@ int finish_trace(rthx_domain* dom, const rthx_trace_args* a, const TracePlan& p,
                  double t0);
 
 // The whole of one device's trace (validated arguments, any device state).
-int trace_exchange_one(rthx_domain* dom, const rthx_trace_args* a, rthx_result* res) {
+// ray_begin: the first ray id of every row (rthx_trace_exchange_rays); it
+// travels in the plan, so a re-trace or a completed async launch keeps it.
+int trace_exchange_one(rthx_domain* dom, const rthx_trace_args* a, rthx_result* res, int64_t ray_begin = 0) {
   const double t0 = now_ms();
   HIP_TRY(hipSetDevice(dom->device), "hipSetDevice");
   // An unread async trace on this result is replaced by this one (stream
@@ -1014,6 +1017,7 @@ int trace_exchange_one(rthx_domain* dom, const rthx_trace_args* a, rthx_result* 
   const bool superseding = res->pending;
   res->valid = false;
   TracePlan p;
+  p.ray_base = ray_begin;
   int rc = plan_trace_split(dom, a, p);
   if (rc) return rc;
   if (res->device >= 0 && res->device != dom->device) return fail(RTHX_EINVAL, "result bound to another device");
@@ -1290,6 +1294,20 @@ RTHX_EXPORT int rthx_trace_exchange(rthx_domain* dom, const rthx_trace_args* a, 
   return trace_exchange_one(dom, a, res);
 }
 
+RTHX_EXPORT int rthx_trace_exchange_rays(rthx_domain* dom, const rthx_trace_args* a, int64_t ray_begin,
+                                         rthx_result* res) {
+  // (the ray range first: it is checked whatever else the call was given)
+  if (!a) return fail(RTHX_EINVAL, "null argument");
+  if (ray_begin < 0) return fail(RTHX_EINVAL, "negative ray_begin");
+  if (a->rays_per_emitter < 0 || a->rays_per_emitter > 0xFFFFFFFFll)
+    return fail(RTHX_ERANGE, "rays_per_emitter must be in [0, 2^32)");
+  if (ray_begin > 0xFFFFFFFFll || ray_begin + a->rays_per_emitter > 0xFFFFFFFFll)
+    return fail(RTHX_ERANGE, "ray_begin + rays_per_emitter must be below 2^32");
+  if (!dom || !res) return fail(RTHX_EINVAL, "null argument");
+  if (a->device != dom->device) return fail(RTHX_EINVAL, "args.device differs from the domain's device");
+  return trace_exchange_one(dom, a, res, ray_begin);
+}
+
 RTHX_EXPORT int rthx_result_get_info(const rthx_result* res, rthx_result_info* info) {
   if (!res || !info) return fail(RTHX_EINVAL, "null argument");
   if (int rc = ready(res)) return rc;
@@ -1560,7 +1578,9 @@ RTHX_EXPORT int rthx_multi_trace_exchange(rthx_multi* m, const rthx_trace_args* 
     (void)hipSetDevice(res->device);
     rthx::DevBuf* all[] = {&res->stage_cols, &res->stage_cnt, &res->row_nnz, &res->row_tallied, &res->row_off,
                            &res->totals,     &res->cols,      &res->cnt,     &res->dense,       &res->rec_ids,
-                           &res->rec_ok,     &res->rec_orig,  &res->rec_end, &res->lb_status, &res->lb_totals, &res->arrive};
+                           &res->rec_ok,     &res->rec_orig,  &res->rec_end, &res->lb_status, &res->lb_totals, &res->arrive,
+                           &res->acc_off,    &res->acc_cols,  &res->acc_cnt, &res->acc_len,   &res->acc_totals,
+                           &res->acc_mark,   &res->acc_err};
     for (rthx::DevBuf* b : all) b->release();
     res->lb_epoch = 0;
     res->device = -1;

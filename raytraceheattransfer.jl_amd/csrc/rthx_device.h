@@ -184,6 +184,7 @@ struct TraceParams {
   int32_t mixed;           // MLAT kernels: some coarse box has no single beta in `bin` (walk_ml)
   double beta_uniform;     // beta of fine face 0 in `bin` (uniform path, traceRay.jl:6-11)
   double inv_beta_uniform; // 1 / beta_uniform, +inf when beta_uniform <= 0 (then every free path is inf)
+  int64_t ray_base;        // first ray id: the row traces rays ray_base + [0, R) (rthx_trace_exchange_rays)
 };
 
 // ---------------------------------------------------------------------------

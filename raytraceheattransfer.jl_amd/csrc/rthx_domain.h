@@ -21,6 +21,7 @@ namespace rthx {
 // split, LDS histogram layout).
 struct TracePlan {
   int64_t N = 0, R = 0, end = 0, n_rows = 0, split = 1, row_cap = 1, hash_cap = 0, bm_words = 0, part_cap = 0;
+  int64_t ray_base = 0;     // first ray id (rthx_trace_exchange_rays); sizes nothing
   bool part_lists = false;  // split hash rows: sorted part lists + part_merge_kernel (else the last part merges)
   int tally = 1;            // rthx_kernels.h Tally (kTallyU16)
   int clds = 0;             // rthx_kernels.h LaunchCfg::clds
@@ -72,6 +73,14 @@ struct rthx_result {
   int64_t lb_hint_shape[3] = {0, 0, 0};  // its (N, rows, R)
   rthx::HostBuf h_totals;  // pinned copy of a look-back launch's totals
   rthx::DevBuf fvals;      // F_raw values (rthx_result_copy_F)
+  // rthx_result_accumulate: the merged CSR is written here and swapped with
+  // row_off / cols / cnt (the old arrays serve the next accumulate); the
+  // merged rows' lengths, per entry of the added block the matches before it
+  // in its row, and the totals (rthx_assemble.h kAccTotals); acc_err: the
+  // rows' variances and their sum / maximum (rthx_result_sampling_error)
+  rthx::DevBuf acc_off, acc_cols, acc_cnt, acc_len, acc_mark, acc_totals, acc_err;
+  hipEvent_t acc_ev[2] = {nullptr, nullptr};  // around the last accumulate's kernels
+  double acc_ms = 0.0;                        // their device time (rthx_result_accumulate_ms)
   // rthx_result_copy_F_csc: radix-sort keys / counts (double-buffered), the
   // sort's scratch, row sums, and the CSC arrays before their host copy
   rthx::DevBuf csc_keys[2], csc_vals[2], csc_tmp, csc_rowsum, csc_colptr, csc_rowval, csc_nz;
@@ -106,10 +115,12 @@ struct rthx_result {
     if (pending && device >= 0) (void)hipDeviceSynchronize();  // (a destroyed result's launch must not outlive its buffers)
     for (auto& e : pend_ev)
       if (e) (void)hipEventDestroy(e);
+    for (auto& e : acc_ev)
+      if (e) (void)hipEventDestroy(e);
     rthx::DevBuf* all[] = {&stage_cols, &stage_cnt, &row_nnz,  &row_tallied, &row_off,  &totals, &cols,
                      &cnt,        &dense,     &rec_ids,  &rec_ok,      &rec_orig, &rec_end, &lb_status, &lb_totals, &fvals, &arrive,
                      &csc_keys[0], &csc_keys[1], &csc_vals[0], &csc_vals[1], &csc_tmp, &csc_rowsum, &csc_colptr,
-                     &csc_rowval, &csc_nz};
+                     &csc_rowval, &csc_nz, &acc_off, &acc_cols, &acc_cnt, &acc_len, &acc_mark, &acc_totals, &acc_err};
     for (rthx::DevBuf* b : all) b->release();
     h_cols.release();
     h_cnt.release();

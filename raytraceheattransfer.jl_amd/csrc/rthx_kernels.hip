@@ -419,7 +419,7 @@ __device__ __forceinline__ uint32_t hash_emit_bitmap(const uint32_t* keys, const
   return total;
 }
 
-template <bool UNIFORM, int TALLY, bool FAITHFUL, bool SINGLE, bool REC, bool SPLIT, bool AXIS, int CL>
+template <bool UNIFORM, int TALLY, bool FAITHFUL, bool SINGLE, bool REC, bool SPLIT, bool AXIS, int CL, bool RBASE>
 __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_exchange_kernel(const DevDomain* __restrict__ Dp,
                                                                      TraceParams P, TallyParams T,
                                                                      RecordParams rec) {
@@ -461,8 +461,20 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
   const int64_t slot = trow;
   const int64_t part = tpart;
   const uint32_t chunk = SPLIT ? (uint32_t)((P.R + parts - 1) / parts) : (uint32_t)P.R;
-  const int64_t r_begin = SPLIT ? (int64_t)(tpart * chunk) : 0;
-  const int64_t r_end = SPLIT ? (r_begin + chunk < P.R ? r_begin + chunk : P.R) : P.R;
+  // Ray ids are absolute: the row's rays are ray_base + [0, R)
+  // (rthx_trace_exchange_rays; ray_base + R < 2^32), and every Philox counter
+  // and group of four below is formed from the absolute id.  The SINGLE
+  // kernels read the base only in their RBASE instances: with the base a
+  // constant 0 the first group and the first round's range test fold away,
+  // which is worth 2.8 % of the headline rate; the host
+  // launches RBASE only for a base that is not 0.
+  constexpr bool kBase = RBASE || !SINGLE;
+  const int64_t ray_base = kBase ? P.ray_base : 0;
+  const int64_t p_begin = SPLIT ? (int64_t)(tpart * chunk) : 0;
+  // (kBase: a part that begins past the row's end is clamped before the base is added)
+  const int64_t r_begin = kBase ? ray_base + (p_begin < P.R ? p_begin : P.R) : p_begin;
+  const int64_t r_end = kBase ? ray_base + (SPLIT ? (p_begin + chunk < P.R ? p_begin + chunk : P.R) : P.R)
+                              : (SPLIT ? (r_begin + chunk < P.R ? r_begin + chunk : P.R) : P.R);
   const int64_t g = P.g_begin + slot * P.g_stride;
   constexpr bool PACK16 = TALLY == kTallyU16, HASH = TALLY == kTallyHash;
   const int64_t n_words = HASH ? 2 * (int64_t)T.hash_cap + T.bm_words : PACK16 ? (T.n_emitters + 1) / 2 : T.n_emitters;
@@ -544,7 +556,7 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
   };
   auto record = [&](uint32_t r, int a, double ox, double oy, double px, double py) {
     if (REC && rec_slot >= 0) {
-      size_t k = (size_t)rec_slot * (size_t)P.R + (size_t)r;
+      size_t k = (size_t)rec_slot * (size_t)P.R + (size_t)(r - (uint32_t)ray_base);
       rec.ok[k] = a >= 0 ? 1 : 0;
       rec.orig[2 * k] = ox; rec.orig[2 * k + 1] = oy;
       rec.end[2 * k] = px; rec.end[2 * k + 1] = py;
@@ -587,7 +599,7 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
     // group's four rays r = 4q + k with pw = word k, k uniform.  The round
     // count is uniform over the workgroup; the last round may be partial
     // (the lanes with q < q1).  Only the first round (rb not a
-    // multiple of four: a split part) and the round that holds group q1 - 1
+    // multiple of four: a split part, or a ray range that starts there) and the round that holds group q1 - 1
     // (re not a multiple of four) can hold rays outside [rb, re): that is a
     // scalar test per round, and only those rounds mask their rays by range.
     // (the quotient comes off the VALU: back into a scalar register, so that
@@ -1277,9 +1289,14 @@ static int device_cus() {
   return n;
 }
 
-template <bool UNIFORM, int TALLY, bool FAITHFUL, bool SINGLE, bool REC, bool SPLIT, bool AXIS, int CL = 0>
+template <bool UNIFORM, int TALLY, bool FAITHFUL, bool SINGLE, bool REC, bool SPLIT, bool AXIS, int CL = 0,
+          bool RBASE = false>
 static hipError_t launch_trace_t(const LaunchCfg& L) {
-  auto kern = trace_exchange_kernel<UNIFORM, TALLY, FAITHFUL, SINGLE, REC, SPLIT, AXIS, CL>;
+  // SINGLE kernels: a ray base that is not 0 runs the RBASE instance (the
+  // others read TraceParams::ray_base as it is)
+  if constexpr (SINGLE && !RBASE)
+    if (L.P.ray_base != 0) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, SINGLE, REC, SPLIT, AXIS, CL, true>(L);
+  auto kern = trace_exchange_kernel<UNIFORM, TALLY, FAITHFUL, SINGLE, REC, SPLIT, AXIS, CL, RBASE>;
   const int64_t blocks = L.T.n_rows * (SPLIT ? L.T.split : 1);
   // (MLAT kernels: a 64-slot ray queue per wave behind the lattice)
   auto lds_for = [&](int t) { return L.lds_bytes + (CL == 2 && !SINGLE ? (size_t)t * kRaySlotBytes : 0); };

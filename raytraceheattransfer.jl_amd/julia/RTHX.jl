@@ -23,7 +23,7 @@ module RTHX
 
 using SparseArrays
 
-const RTHX_ABI_VERSION = Int32(4)
+const RTHX_ABI_VERSION = Int32(5)
 const RTHX_FLAG_FAITHFUL_SAMPLING = UInt32(0x1)
 
 const LIB = Ref{String}("")
@@ -399,6 +399,30 @@ function computeExchangeFactorsBin(rtm, rays_per_emitter::Integer, nudge, spectr
     finally
         ccall((:rthx_result_destroy, LIB[]), Cvoid, (Ptr{Cvoid},), res[])
     end
+end
+
+# Progressive traces (include/rthx.h): rays [ray_begin, ray_begin + R) of every
+# selected emitter into `res`; dst += src; dst += a device CSR block; the
+# binomial sampling error (rms, max_row) of a result's counts.  `dom` and the
+# results are the library's handles (rthx_domain_create, rthx_result_create).
+trace_exchange_rays!(res::Ptr{Cvoid}, dom::Ptr{Cvoid}, args::Ref{TraceArgs}, ray_begin::Integer) =
+    check(ccall((:rthx_trace_exchange_rays, LIB[]), Cint, (Ptr{Cvoid}, Ptr{TraceArgs}, Int64, Ptr{Cvoid}),
+                dom, args, Int64(ray_begin), res))
+
+result_accumulate!(dst::Ptr{Cvoid}, src::Ptr{Cvoid}) =
+    check(ccall((:rthx_result_accumulate, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), dst, src))
+
+result_accumulate_csr!(dst::Ptr{Cvoid}, n_rows::Integer, row_off::Ptr{Int64}, cols::Ptr{UInt32},
+                       counts::Ptr{UInt32}, rays_per_emitter::Integer) =
+    check(ccall((:rthx_result_accumulate_csr, LIB[]), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{UInt32}, Ptr{UInt32}, Int64),
+                dst, Int64(n_rows), row_off, cols, counts, Int64(rays_per_emitter)))
+
+function result_sampling_error(res::Ptr{Cvoid})
+    rms = Ref{Float64}(0.0); max_row = Ref{Float64}(0.0)
+    check(ccall((:rthx_result_sampling_error, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}),
+                res, rms, max_row))
+    return rms[], max_row[]
 end
 
 """

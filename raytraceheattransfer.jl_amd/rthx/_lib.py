@@ -59,6 +59,11 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib.rthx_result_destroy.restype = None
     lib.rthx_trace_exchange.argtypes = [C.c_void_p, C.POINTER(abi.TraceArgs), C.c_void_p]
     lib.rthx_result_get_info.argtypes = [C.c_void_p, C.POINTER(abi.ResultInfo)]
+    lib.rthx_trace_exchange_rays.argtypes = [C.c_void_p, C.POINTER(abi.TraceArgs), C.c_int64, C.c_void_p]
+    lib.rthx_result_accumulate.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rthx_result_accumulate_csr.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.rthx_result_accumulate_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.rthx_result_sampling_error.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.rthx_result_copy_csr.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                          C.POINTER(C.c_uint32)]
     lib.rthx_result_copy_F.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
@@ -301,12 +306,63 @@ class DeviceResult:
         check(self._lib.rthx_result_create(C.byref(h)))
         self.handle = h
 
-    def trace(self, dom, args) -> "DeviceResult":
+    def trace(self, dom, args, ray_begin: int = 0) -> "DeviceResult":
+        """Trace into this result; ``ray_begin`` > 0 traces ray ids
+        [ray_begin, ray_begin + R) of every emitter (rthx_trace_exchange_rays,
+        one device)."""
         if isinstance(dom, MultiDeviceDomain):
+            if ray_begin:
+                raise RthxError("a ray range needs a one-device domain (rthx_trace_exchange_rays)")
             check(self._lib.rthx_multi_trace_exchange(dom.handle, C.byref(args), self.handle))
+        elif ray_begin:
+            check(self._lib.rthx_trace_exchange_rays(dom.handle, C.byref(args), int(ray_begin), self.handle))
         else:
             check(self._lib.rthx_trace_exchange(dom.handle, C.byref(args), self.handle))
         return self
+
+    def accumulate(self, other: "DeviceResult") -> "DeviceResult":
+        """self += other on the device (rthx_result_accumulate): afterwards
+        this result reads like one trace of the summed rays.  The two ray sets
+        must be disjoint (other ray ranges of the seed, or another seed)."""
+        check(self._lib.rthx_result_accumulate(self.handle, other.handle))
+        return self
+
+    def accumulate_csr(self, row_off, cols, counts, rays_per_emitter: int) -> "DeviceResult":
+        """self += a CSR block on this result's device
+        (rthx_result_accumulate_csr): row_off (int64, n_rows + 1, from 0),
+        cols and counts (32-bit) as torch device tensors -- the layout of
+        torch_csr() -- or as raw device pointers (ints) with row_off a
+        (pointer, n_rows) pair."""
+        if hasattr(row_off, "data_ptr"):
+            import torch
+
+            if row_off.dtype != torch.int64 or cols.element_size() != 4 or counts.element_size() != 4:
+                raise RthxError("accumulate_csr needs int64 row offsets and 32-bit cols / counts")
+            if not (row_off.is_contiguous() and cols.is_contiguous() and counts.is_contiguous()):
+                raise RthxError("accumulate_csr needs contiguous tensors")
+            torch.cuda.current_stream(row_off.device).synchronize()  # (the tensors' producers; the library has its own stream)
+            n_rows = row_off.numel() - 1
+            ptrs = (row_off.data_ptr(), cols.data_ptr() if cols.numel() else None,
+                    counts.data_ptr() if counts.numel() else None)
+        else:
+            ptr, n_rows = row_off
+            ptrs = (ptr, cols, counts)
+        check(self._lib.rthx_result_accumulate_csr(self.handle, int(n_rows), C.c_void_p(ptrs[0]), C.c_void_p(ptrs[1]),
+                                                   C.c_void_p(ptrs[2]), int(rays_per_emitter)))
+        return self
+
+    def accumulate_ms(self) -> float:
+        """Device time of the last accumulate into this result (hipEvents)."""
+        ms = C.c_double(0.0)
+        check(self._lib.rthx_result_accumulate_ms(self.handle, C.byref(ms)))
+        return ms.value
+
+    def sampling_error(self):
+        """(rms, max_row): the binomial sampling error of F_raw = count /
+        tallied over the traced rows (rthx_result_sampling_error)."""
+        rms, mx = C.c_double(0.0), C.c_double(0.0)
+        check(self._lib.rthx_result_sampling_error(self.handle, C.byref(rms), C.byref(mx)))
+        return rms.value, mx.value
 
     def info(self) -> dict:
         inf = abi.ResultInfo()

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-RTHX_ABI_VERSION = 4
+RTHX_ABI_VERSION = 5
 
 RTHX_OK = 0
 RTHX_EINVAL = -1
@@ -294,7 +294,12 @@ EXPORTED_SYMBOLS = (
     "rthx_result_create",
     "rthx_result_destroy",
     "rthx_trace_exchange",
+    "rthx_trace_exchange_rays",
     "rthx_result_get_info",
+    "rthx_result_accumulate",
+    "rthx_result_accumulate_csr",
+    "rthx_result_accumulate_ms",
+    "rthx_result_sampling_error",
     "rthx_result_copy_csr",
     "rthx_result_copy_rays",
     "rthx_result_copy_F",

@@ -704,3 +704,164 @@ def trace_bands_row_sharded(dom, rays: int, group=None, seed: int = 1, nudge: fl
     return owned, {"world": W, "rank": rank, "rays_per_emitter": R, "traces": infos, "timeline": timeline,
                    "wall_s": wall, "call_s": total, "last_parts": last_parts,
                    "owner": {b: i % W for i, (b, _) in enumerate(traced)}}
+
+
+# ---------------------------------------------------------------------------
+# Ray-sharded traces (SURVEY.md §5 "ray-sharded variant"): every rank traces
+# all rows over 1/W of the ray ids, so the ranks are balanced by construction
+# whatever the row costs, and assembling F is a sum of W CSRs over the same
+# rows -- rthx_result_accumulate_csr on the owner -- instead of a merge of
+# disjoint rows.
+# ---------------------------------------------------------------------------
+def accumulate_csr_host(a, b, n: int):
+    """The sum of two count matrices over the same rows, on the host (numpy):
+    a and b are (row_ptr, cols, counts) with equally many rows and columns
+    below n; rows of the sum are column-ascending, equal columns add their
+    counts.  The reference of rthx_result_accumulate, and the fold of a gloo
+    group's blocks."""
+    rpa, ca, va = (np.asarray(x) for x in a)
+    rpb, cb, vb = (np.asarray(x) for x in b)
+    rows = len(rpa) - 1
+    if len(rpb) - 1 != rows:
+        raise ValueError("the blocks have different row counts")
+    n = max(int(n), 1)
+    keys = []
+    for rp, c in ((rpa, ca), (rpb, cb)):
+        nnz = int(rp[-1]) - int(rp[0])
+        r = np.repeat(np.arange(rows, dtype=np.int64), np.diff(rp))
+        c = np.asarray(c[:nnz], dtype=np.int64)
+        if nnz and (c.min() < 0 or c.max() >= n):
+            raise ValueError("column out of range")
+        keys.append(r * n + c)
+    vals = np.concatenate([np.asarray(va[:len(keys[0])], dtype=np.uint64), np.asarray(vb[:len(keys[1])], dtype=np.uint64)])
+    u, inv = np.unique(np.concatenate(keys), return_inverse=True)
+    s = np.zeros(len(u), dtype=np.uint64)
+    np.add.at(s, inv.reshape(-1), vals)
+    if len(s) and int(s.max()) > 0xFFFFFFFF:
+        raise OverflowError("a summed count does not fit 32 bits")
+    row_ptr = np.zeros(rows + 1, dtype=np.int64)
+    np.cumsum(np.bincount(u // n, minlength=rows)[:rows] if rows else np.zeros(0, dtype=np.int64), out=row_ptr[1:])
+    return row_ptr, (u % n).astype(np.int32), s.astype(np.uint32)
+
+
+def _default_nudge(nudge):
+    return 10_000 * np.finfo(np.float64).eps if nudge is None else nudge
+
+
+def _trace_ray_range(res, dd, n: int, bin0: int, ray_begin: int, n_rays: int, nudge: float, seed: int, device: int,
+                     faithful: bool, emitter_begin: int = 0, emitter_end=None, emitter_stride: int = 1):
+    """Rays [ray_begin, ray_begin + n_rays) of the selected rows into `res`, counts left on the device."""
+    from . import abi
+    from ._lib import make_args
+
+    flags = abi.RTHX_FLAG_DEVICE_ONLY | (abi.RTHX_FLAG_FAITHFUL_SAMPLING if faithful else 0)
+    args, keep = make_args(bin0, n_rays, nudge, seed, emitter_begin, n if emitter_end is None else emitter_end,
+                           emitter_stride, device, flags)
+    res.trace(dd, args, ray_begin=ray_begin)
+    del keep
+    return res
+
+
+def trace_ray_sharded(dom, rays_per_emitter: int, world: int, spectral_bin: int = 1, nudge: float = None,
+                      seed: int = 1, device: int = 0, faithful: bool = False, group=None, dst: int = 0,
+                      emitter_begin: int = 0, emitter_end=None, emitter_stride: int = 1):
+    """One bin traced as W ray shards: rank k traces every selected row over
+    the ray ids rthx.direct.ray_shard(k, W, R), and the owner `dst` folds the
+    W blocks with rthx_result_accumulate_csr.  The counts are those of one
+    trace of R rays per emitter, bit for bit.
+
+    group=None: the emulated form -- the W ranks run one after another on
+    `device` (as EmulatedBandComm does for row shards): every shard is traced
+    into a scratch result, copied out as the block a gather would deliver
+    (torch tensors on the device) and folded into the owner's result.
+    Returns the owner's DeviceResult.
+
+    With a torch.distributed group of size `world` (one process per GPU; NCCL
+    = RCCL): this rank traces its shard on `device`, the blocks are gathered
+    to rank `dst` as device tensors and folded there; the other ranks return
+    None."""
+    from .direct import ray_shard
+    from ._lib import DeviceResult, device_domain
+
+    nudge = _default_nudge(nudge)
+    n = dom.flat().n_emitters
+    dd = device_domain(dom, device)
+    bin0 = spectral_bin - 1
+    sel = dict(emitter_begin=emitter_begin, emitter_end=emitter_end, emitter_stride=emitter_stride)
+    if group is None:
+        owner, scratch = DeviceResult(), DeviceResult()
+        try:
+            b, e = ray_shard(dst, world, rays_per_emitter)
+            _trace_ray_range(owner, dd, n, bin0, b, e - b, nudge, seed, device, faithful, **sel)
+            for k in range(world):
+                if k == dst:
+                    continue
+                b, e = ray_shard(k, world, rays_per_emitter)
+                _trace_ray_range(scratch, dd, n, bin0, b, e - b, nudge, seed, device, faithful, **sel)
+                row_off, pairs, _d = scratch.torch_csr()
+                owner.accumulate_csr(row_off, pairs[0], pairs[1], e - b)
+        except Exception:
+            owner.close()
+            raise
+        finally:
+            scratch.close()
+        return owner
+    import torch.distributed as dist
+
+    rank = dist.get_rank(group)
+    if dist.get_world_size(group) != world:
+        raise ValueError("world differs from the group's size")
+    b, e = ray_shard(rank, world, rays_per_emitter)
+    res = _trace_ray_range(DeviceResult(), dd, n, bin0, b, e - b, nudge, seed, device, faithful, **sel)
+    row_off, pairs, _d = res.torch_csr()
+    blocks = gather_ray_shards(row_off, pairs, group=group, dst=dst)
+    if blocks is None:
+        res.close()
+        return None
+    for k, (ro, pr) in enumerate(blocks):
+        if k == rank:
+            continue
+        kb, ke = ray_shard(k, world, rays_per_emitter)
+        res.accumulate_csr(ro, pr[0].contiguous(), pr[1].contiguous(), ke - kb)
+    return res
+
+
+def gather_ray_shards(row_off, pairs, group=None, dst: int = 0):
+    """Every rank's CSR block over the same rows -- row_off (int64,
+    n_rows + 1, from 0) and the int32 [2, nnz] (col, count) tensor, on the
+    group's device -- to rank `dst`: a list of W (row_off, pairs) there, None
+    elsewhere.  The blocks overlap in rows (ray shards), so unlike gather_csr
+    nothing is merged here: the owner sums them (fold_ray_shards_host, or
+    rthx_result_accumulate_csr on the device)."""
+    import torch
+    import torch.distributed as dist
+
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    dev = row_off.device
+    nnz = int(pairs.shape[1])
+    sizes = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
+    dist.all_gather(sizes, torch.tensor([nnz], dtype=torch.int64, device=dev), group=group)
+    sizes = [int(x.item()) for x in sizes]
+    buf = torch.zeros((2, max(max(sizes), 1)), dtype=torch.int32, device=dev)
+    buf[:, :nnz] = pairs
+    row_off = row_off.contiguous()
+    out_r = [torch.empty_like(row_off) for _ in range(world)] if rank == dst else None
+    out_p = [torch.empty_like(buf) for _ in range(world)] if rank == dst else None
+    dist.gather(row_off, out_r, dst=dst, group=group)
+    dist.gather(buf, out_p, dst=dst, group=group)
+    if rank != dst:
+        return None
+    return [(out_r[k], out_p[k][:, :sizes[k]]) for k in range(world)]
+
+
+def fold_ray_shards_host(blocks, n: int):
+    """The sum of gathered ray-shard blocks on the host (a gloo group's cpu
+    tensors, or numpy triples): (row_ptr, cols, counts) over the blocks' rows."""
+    acc = None
+    for ro, pr in blocks:
+        ro = np.asarray(ro.cpu() if hasattr(ro, "cpu") else ro, dtype=np.int64)
+        pr = np.asarray(pr.cpu() if hasattr(pr, "cpu") else pr)
+        blk = (ro, pr[0].astype(np.int32), np.ascontiguousarray(pr[1]).view(np.uint32) if pr.dtype == np.int32
+               else pr[1].astype(np.uint32))
+        acc = blk if acc is None else accumulate_csr_host(acc, blk, n)
+    return acc

@@ -63,6 +63,23 @@ class Scene3D:
             res.close()
         return rp, cols, cnt, info
 
+    def trace_result(self, rays_per_emitter: int, seed: int = 1, faithful: bool = False, result=None):
+        """rthx_trace_exchange_3d into a DeviceResult that is returned with
+        its counts on the device (to accumulate traces of different seeds:
+        DeviceResult.accumulate); `result`: one to reuse."""
+        from ._lib import DeviceResult, check, make_args
+
+        flags = (abi.RTHX_FLAG_FAITHFUL_SAMPLING if faithful else 0) | abi.RTHX_FLAG_DEVICE_ONLY
+        args, _keep = make_args(0, rays_per_emitter, 0.0, seed, 0, self.n, 1, self.device, flags)
+        res = DeviceResult() if result is None else result
+        try:
+            check(self._lib.rthx_trace_exchange_3d(self.handle, C.byref(args), res.handle))
+        except Exception:
+            if result is None:
+                res.close()
+            raise
+        return res
+
     def stats(self) -> dict:
         """rthx_scene3d_stats: triangles, BVH inner nodes, depth, LDS bytes per workgroup."""
         from ._lib import check
