@@ -603,6 +603,17 @@ RTHX_EXPORT int rthx_domain_create(const rthx_domain_desc* desc, int32_t device,
       L.bytes = (int32_t)off;
       L.inv_x = (double)lnx / (xs[lnx] - xs[0]);
       L.inv_y = (double)lny / (ys[lny] - ys[0]);
+      // RTHX_LAT_GUESS_SCALE (tests): the first guess of the cell scaled.  The
+      // guess only seeds the exact search against xs / ys, so the counts are
+      // the same for any scale; a scale off 1 sends most rays through the
+      // LAT ray's fix-up block (rthx_device.h lat_ray_fixup).
+      if (const char* gs = rthx::knob("RTHX_LAT_GUESS_SCALE")) {
+        const double sc = std::strtod(gs, nullptr);
+        if (std::isfinite(sc) && sc > 0.0) {
+          L.inv_x *= sc;
+          L.inv_y *= sc;
+        }
+      }
       std::vector<uint4> blob(off / 16);
       char* b = reinterpret_cast<char*>(blob.data());
       std::memset(b, 0, off);

@@ -914,12 +914,33 @@ __device__ __forceinline__ void emit_volume(const Emitter& e, double eta, const 
 
 // The coarse polygon a SINGLE-domain workgroup traces in, staged in LDS:
 // its record, solid-wall mask and fine point-location grid.
+// LAT kernels keep the lattice's scalars there in the fine grid's place
+// (they locate on the lattice, not on the grid), read once per workgroup from
+// the domain record and broadcast-read from LDS at their point of use: no
+// scalar load and no load from a uniform global address inside a ray.
+struct LatGrid {
+  double x0, y0;        // xs[0], ys[0]
+  double inv_x, inv_y;  // LatticeLayout: first guess of the cell
+  int32_t nxm1, nym1;   // nx - 1, ny - 1 (the guess's clamp)
+  int32_t nx;
+  int32_t off_ys;       // LatticeLayout::off_ys
+};
+static_assert(sizeof(LatGrid) == sizeof(DevGrid), "LatGrid overlays SingleCoarse::grid");
+
 struct SingleCoarse {
   DevPoly poly;
-  DevGrid grid;
+  union {
+    DevGrid grid;
+    LatGrid lat;  // LAT kernels
+  };
   uint32_t solid;
-  int32_t count;  // fine polygons (first = 0)
+  union {
+    int32_t count;       // fine polygons (first = 0)
+    int32_t n_surfaces;  // LAT kernels (they never read the count)
+  };
+  double inv_beta;  // LAT kernels: TraceParams::inv_beta_uniform
 };
+static_assert(sizeof(SingleCoarse) == 192, "SingleCoarse fills the padding it had: the kernels' static LDS is unchanged");
 
 // ---------------------------------------------------------------------------
 // traceRayUniform (traceRay.jl:20-70) and traceRayVariable (:73-147).
@@ -1109,6 +1130,168 @@ __device__ __forceinline__ int segment_lat(const DevDomain& D, const TraceParams
   // 19.92 -> 19.58 ms, profiles/round6/ab/lat_fsurf.log)
   // (n_fine <= kLatMaxDim^2 = 2^24 cells of 16 bytes: a 32-bit byte offset)
   return ld_off32(D.f_surf, ((uint32_t)(G.identity ? cell : D.lat_map[cell]) << 4) + ((uint32_t)w << 2));
+}
+
+// ---------------------------------------------------------------------------
+// The LAT ray of the exchange kernel (uniform path): segment_lat<true>
+// written as one basic block for the common ray, lat_ray_fast, and one cold
+// continuation for every other ray, lat_ray_fixup.
+//
+// lat_ray_fast runs segment_lat's expressions in segment_lat's order with
+// every case decided by a select: the coarse two-wall test with the winner's
+// division unconditional (u = +inf and k = 0 selected where no wall
+// qualifies), gas or wall as a select of t, the move, both lattice guesses
+// with their paired bound reads, the cell, the fine wall of the end cell
+// from the bounds already read (box_hit_in's expressions, its tie order
+// formed by mask logic on the compare results) and the f_surf load under the
+// wall lanes' mask.  Beside the result it forms the predicate `cold`: a lane
+// is cold when
+//   - the ray is neither gas nor solid wall (lost),
+//   - its x or y guess missed, i.e. not lo <= x < hi (the correction walk
+//     must run),
+//   - no fine wall qualified for a wall ray (w must be 0),
+//   - its wall is not solid in f_surf (lost),
+//   - the caller's `cold0` (an edge round's ray outside the row's range).
+// Bit-exactness: for a lane that is not cold every select above took the
+// branch segment_lat takes -- gas or wall, so t and the move are
+// segment_lat's; the guess hit, so lattice_index returns the guess at its
+// first test and (i, j), the cell and the bounds are the same; a fine wall
+// qualified, so w is box_hit_in's -- and the operations are the same ones on
+// the same operands: the accepted result is segment_lat's.  A cold lane's
+// fast result is discarded: lat_ray_fixup continues the same ray from its
+// end point, which is segment_lat's for every ray that has one (S, u, k and
+// t do not depend on the guess), through segment_lat's own sequence from
+// there: lattice_index's correction walk from the guess, the cell,
+// box_hit_in, f_surf.  The continuation needs nothing of the ray but what
+// the fast body holds at its end (end point, direction, three masks), so no
+// register is kept for it.
+// No sign-bit tests: dx < 0 and dy < 0 stay fp64 compares.
+// ---------------------------------------------------------------------------
+struct LatRay {
+  double px, py;  // in: start point; out: end point (of a ray that is not lost)
+  double dx, dy;
+  double S;       // free path
+  bool gas;       // out: absorbed by the gas (else by a wall, if not lost)
+  bool lost;      // out: neither gas nor solid wall
+  bool cold;      // out
+};
+
+// lattice_index's correction from the clamped guess i (0 <= i < n), the
+// downward walk and the upward walk as one loop: a step down when
+// i > 0 && x < b[i], else a step up when i < n - 1 && !(x < b[i + 1]).  The
+// same index as the two loops one after the other: once no step down is
+// possible none becomes possible again (a step up to i + 1 was taken because
+// !(x < b[i + 1]), which is the down test there), so every down step comes
+// before every up step, as in lattice_index.
+__device__ __forceinline__ int lattice_walk(const double RTHX_LDS* b, int nm1, int i, double x) {
+#pragma unroll 1
+  while (true) {
+    const bool dn = i > 0 && x < b[i];
+    const bool up = !dn && i < nm1 && !(x < b[i + 1]);
+    if (!(dn | up)) break;
+    i += dn ? -1 : 1;
+  }
+  return (b[i] <= x && x < b[i + 1]) ? i : -1;
+}
+
+// The clamped first guess of lattice_index (the same two instructions).
+__device__ __forceinline__ int lattice_guess(double x, double x0, double inv, int nm1) {
+  int i;
+  __asm__("v_cvt_i32_f64 %0, %1" : "=v"(i) : "v"(__dmul_rn(x - x0, inv)));
+  __asm__("v_med3_i32 %0, %1, 0, %2" : "=v"(i) : "v"(i), "v"(nm1));
+  return i;
+}
+
+// 0: the f_surf load of lat_ray_fast runs for every lane (A/B knob)
+#ifndef RTHX_LAT_SURF_MASKED
+#define RTHX_LAT_SURF_MASKED 1
+#endif
+
+// INSIDE: as segment_lat.  identity: LatticeLayout::identity (uniform).
+// Returns the absorber of a lane that is not cold.
+template <bool INSIDE>
+__device__ __forceinline__ int lat_ray_fast(const DevDomain& D, double eta, const SingleCoarse& sc,
+                                            const char RTHX_LDS* lat_base, bool identity, bool cold0, LatRay& r) {
+  const double ox = r.px, oy = r.py, dx = r.dx, dy = r.dy, S = r.S;
+  const double cx0 = sc.poly.x[0], cx1 = sc.poly.x[1], cy0 = sc.poly.y[0], cy1 = sc.poly.y[2];
+  const bool xdn = dx < 0.0, ydn = dy < 0.0;
+  const bool y_first = ydn | xdn;
+  double u;
+  int k;
+  if (INSIDE) {
+    // dist_in_box / box_hit_in, the division unconditional
+    const double xb = xdn ? cx0 : cx1, yb = ydn ? cy0 : cy1;
+    const double sx = xb - ox, sy = yb - oy;
+    const double mx = __dmul_rn(fabs(sx), fabs(dx)), my = __dmul_rn(fabs(sy), fabs(dy));
+    const bool vx = (fabs(dx) >= 1e-10) & (mx > 0.0);
+    const bool vy = (fabs(dy) >= 1e-10) & (my > 0.0);
+    const double cx = __dmul_rn(fabs(sx), fabs(dy)), cy = __dmul_rn(fabs(sy), fabs(dx));
+    const bool xw = vx & (!vy | (y_first & (cx < cy)) | (!y_first & !(cy < cx)));
+    const bool any = vx | vy;
+    const double q = div_pos(fabs(xw ? sx : sy), fabs(xw ? dx : dy));
+    u = any ? q : __builtin_inf();
+    k = any ? (xw ? (xdn ? 3 : 1) : (ydn ? 0 : 2)) : 0;
+  } else {
+    // (a surface emitter's rays: segment_lat's choice of the test)
+    if (cx0 <= ox && ox < cx1 && cy0 <= oy && oy < cy1)
+      u = dist_in_box(ox, oy, dx, dy, xdn ? cx0 : cx1, ydn ? cy0 : cy1, k);
+    else
+      u = dist_to_box(ox, oy, dx, dy, cx0, cx1, cy0, cy1, k);
+  }
+  const bool gas = S < u;
+  const bool wall = !gas & (((sc.solid >> k) & 1u) != 0u);
+  const bool lost = !(gas | wall);
+  const double t = (gas ? S : u) - eta;
+  const double px = ox + __dmul_rn(t, dx);
+  const double py = oy + __dmul_rn(t, dy);
+  r.px = px;
+  r.py = py;
+  r.gas = gas;
+  r.lost = lost;
+  // both guesses, then both paired bound reads, then the four compares
+  const LatGrid& G = sc.lat;
+  const double RTHX_LDS* xs = (const double RTHX_LDS*)lat_base;
+  const double RTHX_LDS* ys = (const double RTHX_LDS*)(lat_base + G.off_ys);
+  const int i = lattice_guess(px, G.x0, G.inv_x, G.nxm1);
+  const int j = lattice_guess(py, G.y0, G.inv_y, G.nym1);
+  const double xlo = xs[i], xhi = xs[i + 1], ylo = ys[j], yhi = ys[j + 1];
+  const bool hit = (xlo <= px) & (px < xhi) & (ylo <= py) & (py < yhi);
+  int f = lat_cell(i, j, G.nx);
+  if (!identity) f = D.lat_map[f];
+  // the fine wall of cell (i, j): box_hit_in on the bounds just read
+  const double sx = (xdn ? xlo : xhi) - px, sy = (ydn ? ylo : yhi) - py;
+  const double mx = __dmul_rn(fabs(sx), fabs(dx)), my = __dmul_rn(fabs(sy), fabs(dy));
+  const bool vx = (fabs(dx) >= 1e-10) & (mx > 0.0);
+  const bool vy = (fabs(dy) >= 1e-10) & (my > 0.0);
+  const double cx = __dmul_rn(fabs(sx), fabs(dy)), cy = __dmul_rn(fabs(sy), fabs(dx));
+  const bool xw = vx & (!vy | (y_first & (cx < cy)) | (!y_first & !(cy < cx)));
+  const int wl = xw ? (xdn ? 3 : 1) : (ydn ? 0 : 2);
+  // (f < n_fine and wl < 4 for every lane, cold ones included: the guesses
+  // are clamped.  The load still runs for the wall lanes only: for every
+  // lane it is 64 scattered L2 reads a ray)
+  int surf = -1;
+  if (!RTHX_LAT_SURF_MASKED || wall) surf = ld_off32(D.f_surf, ((uint32_t)f << 4) + ((uint32_t)wl << 2));
+  const int a = gas ? sc.n_surfaces + f : surf;
+  r.cold = cold0 | lost | !hit | (wall & !(vx | vy)) | (a < 0);
+  return a;
+}
+
+// The cold lanes' continuation (see above): the absorber, -1 for a lost ray.
+__device__ __forceinline__ int lat_ray_fixup(const DevDomain& D, const SingleCoarse& sc,
+                                             const char RTHX_LDS* lat_base, bool identity, const LatRay& r) {
+  if (r.lost) return -1;  // an open wall of the only polygon leads outside
+  const double px = r.px, py = r.py, dx = r.dx, dy = r.dy;
+  const LatGrid& G = sc.lat;
+  const double RTHX_LDS* xs = (const double RTHX_LDS*)lat_base;
+  const double RTHX_LDS* ys = (const double RTHX_LDS*)(lat_base + G.off_ys);
+  const int i = lattice_walk(xs, G.nxm1, lattice_guess(px, G.x0, G.inv_x, G.nxm1), px);
+  const int j = lattice_walk(ys, G.nym1, lattice_guess(py, G.y0, G.inv_y, G.nym1), py);
+  if (i < 0 || j < 0) return -1;
+  int f = lat_cell(i, j, G.nx);
+  if (!identity) f = D.lat_map[f];
+  if (r.gas) return sc.n_surfaces + f;
+  const int w = box_hit_in(px, py, dx, dy, dx < 0.0 ? xs[i] : xs[i + 1], dy < 0.0 ? ys[j] : ys[j + 1]).wall;
+  return ld_off32(D.f_surf, ((uint32_t)f << 4) + ((uint32_t)w << 2));
 }
 
 // ---------------------------------------------------------------------------
@@ -1669,11 +1852,14 @@ __device__ __forceinline__ double free_path(const TraceParams& P, const double* 
 }
 
 // free_path(u32(w)), the table log taken from w directly (neg_log_u32).
-template <bool UNIFORM, bool FAITHFUL>
-__device__ __forceinline__ double free_path_u32(const TraceParams& P, const double* tabs, uint32_t w) {
+// LATRAY (the LAT ray, lat_ray_fast): 1 / beta comes from the coarse record
+// in LDS (the same value).
+template <bool UNIFORM, bool FAITHFUL, bool LATRAY = false>
+__device__ __forceinline__ double free_path_u32(const TraceParams& P, const double* tabs, uint32_t w,
+                                                const SingleCoarse* sc = nullptr) {
   if (FAITHFUL) return free_path<UNIFORM, true>(P, tabs, u32(w));
   const double l = neg_log_u32(w, tabs + kLogTableOffset);
-  if (UNIFORM) return l * tabs[kTabInvBeta];  // (P.inv_beta_uniform; l in (0, inf]: inf for beta_uniform <= 0)
+  if (UNIFORM) return l * (LATRAY ? sc->inv_beta : tabs[kTabInvBeta]);  // (P.inv_beta_uniform; l in (0, inf]: inf for beta_uniform <= 0)
   return l;
 }
 
@@ -1710,10 +1896,10 @@ __device__ __forceinline__ RayWords ray_words(const TraceParams& P, const Emitte
 }
 
 // Emission of ray (g, r): point, direction and free path / tau*.
-template <bool UNIFORM, bool FAITHFUL, int EK = kEmitAny>
+template <bool UNIFORM, bool FAITHFUL, int EK = kEmitAny, bool LATRAY = false>
 __device__ __forceinline__ void start_ray_w(const TraceParams& P, const Emitter& e, const double* tabs,
                                             const RayWords& rw, double& px, double& py, double& dx, double& dy,
-                                            double& S) {
+                                            double& S, const SingleCoarse* sc = nullptr) {
   const bool surface = emitter_surface<EK>(e);
   if (surface)
     emit_surface<FAITHFUL>(e, P.eta, rw, tabs, px, py, dx, dy);
@@ -1723,7 +1909,7 @@ __device__ __forceinline__ void start_ray_w(const TraceParams& P, const Emitter&
   // dynamically indexed scratch load)
   uint32_t w_surf = rw.a[3], w_vol = rw.pw;
   __asm__ volatile("" : "+v"(w_surf), "+v"(w_vol));
-  S = free_path_u32<UNIFORM, FAITHFUL>(P, tabs, surface ? w_surf : w_vol);
+  S = free_path_u32<UNIFORM, FAITHFUL, LATRAY>(P, tabs, surface ? w_surf : w_vol, sc);
 }
 
 template <bool UNIFORM, bool FAITHFUL>

@@ -531,6 +531,21 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
       s_single.grid = D.f_grid[0];
       s_single.solid = D.c_solid[0];
       s_single.count = D.f_offset[1];
+      if (CLDS && AXIS) {  // LAT: the lattice's scalars in the fine grid's place (LatGrid)
+        const char RTHX_GLOBAL* blob = (const char RTHX_GLOBAL*)D.lat_blob;
+        LatGrid lg;
+        lg.x0 = *(const double RTHX_GLOBAL*)blob;
+        lg.y0 = *(const double RTHX_GLOBAL*)(blob + D.lat.off_ys);
+        lg.inv_x = D.lat.inv_x;
+        lg.inv_y = D.lat.inv_y;
+        lg.nxm1 = D.lat.nx - 1;
+        lg.nym1 = D.lat.ny - 1;
+        lg.nx = D.lat.nx;
+        lg.off_ys = D.lat.off_ys;
+        s_single.lat = lg;
+        s_single.n_surfaces = D.n_surfaces;
+        s_single.inv_beta = P.inv_beta_uniform;
+      }
     }
   }
   // recorded emitter?  (RayRecorder ids, parallelRayTracing.jl:108)
@@ -587,6 +602,52 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
       tally(a);
       record(r, a, ox, oy, px, py);
     };
+    // The uniform LAT ray: lat_ray_fast as one basic block, then the cold
+    // lanes' continuation lat_ray_fixup under one mask (rthx_device.h), then
+    // one tally for every lane.  A lost ray adds 0 to word 0 and takes 1 off
+    // s_tallied (modulo 2^32: the row's ray count is added at the end), so no
+    // lane counts its tallied rays; cold0: the ray lies outside the row's
+    // range (an edge round), it runs like any other and adds 0.
+    // (The instances that read a ray base keep segment_lat: with the base
+    // live in the loop the fast body's registers no longer fit 64 VGPRs, and
+    // the spilled form measured 1 % slower than segment_lat there,
+    // profiles/round9/ab/regressions_first.log.)
+    constexpr bool LATRAY = CLDS && AXIS && UNIFORM && !RBASE;
+    const bool lat_identity = LATRAY && __builtin_amdgcn_readfirstlane(D.lat.identity) != 0;
+    auto one_ray_lat = [&](uint32_t r, uint32_t pw, bool cold0, auto ek) {
+      constexpr int EK = decltype(ek)::value;
+      const SingleCoarse RTHX_LDS* scl = lds_opaque(&s_single);
+      const SingleCoarse& sc = *(const SingleCoarse*)scl;
+      const double* tab = RTHX_TAB_PTR;
+      const Emitter RTHX_LDS* em = lds_opaque(&s_emit);
+      const Emitter& e = *(const Emitter*)em;
+      const RayWords rw = ray_words<EK>(P, e, (uint32_t)g, r, true, pw, FAITHFUL);
+      LatRay ry;
+      start_ray_w<UNIFORM, FAITHFUL, EK, true>(P, e, (const double*)tab, rw, ry.px, ry.py, ry.dx, ry.dy, ry.S, &sc);
+      const char RTHX_LDS* lat = lds_opaque(cl_base);
+      int a = lat_ray_fast<EK == kEmitVolRect>(D, P.eta, sc, lat, lat_identity, cold0, ry);
+      auto fixup = [&]() {
+        int a2 = -1;
+        if (!cold0) {
+          a2 = lat_ray_fixup(D, sc, lat, lat_identity, ry);
+          if (a2 < 0) atomicSub(&s_tallied, 1u);
+        }
+        return a2;
+      };
+      if constexpr (HASH) {
+        if (ry.cold) a = fixup();
+        if (a >= 0) hash_tally(hist, hist + T.hash_cap, (uint32_t)T.hash_cap - 1u, (uint32_t)T.hash_shift, (uint32_t)a);
+      } else {
+        uint32_t word = PACK16 ? (uint32_t)a >> 1 : (uint32_t)a;
+        uint32_t val = PACK16 ? 1u << ((uint32_t)(a & 1) << 4) : 1u;
+        if (ry.cold) {
+          const int a2 = fixup();
+          word = a2 < 0 ? 0u : PACK16 ? (uint32_t)a2 >> 1 : (uint32_t)a2;
+          val = a2 < 0 ? 0u : PACK16 ? 1u << ((uint32_t)(a2 & 1) << 4) : 1u;
+        }
+        atomicAdd(&hist[word], val);
+      }
+    };
     const uint32_t rb = (uint32_t)r_begin;
     const uint32_t re = (uint32_t)r_end > rb ? (uint32_t)r_end : rb;  // (a part that begins past the row's end is empty)
     const uint32_t q0 = rb >> 2, q1 = (re + 3u) >> 2;
@@ -616,6 +677,29 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
         uint32_t b[4] = {0u, 0u, 0u, 0u};
         if (volume) philox_words(q, (uint32_t)g, 1u, (uint32_t)P.bin, P.key0, P.key1, b);
         const bool edge = (rd == 0u && (rb & 3u) != 0u) || (q_lo + nt >= q1 && (re & 3u) != 0u);
+        if constexpr (LATRAY) {
+          // the four range tests of an edge round ahead of its rays, so that
+          // no scalar branch stands between one ray and the next
+          bool out[4] = {false, false, false, false};
+          if (edge) {
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; ++k) {
+              uint32_t r = 4u * q + k;
+              __asm__ volatile("" : "+v"(r));  // (keeps the range test inside the scalar branch)
+              out[k] = !(r >= rb && r < re);
+            }
+          }
+#if RTHX_ROUND_UNROLL
+#pragma unroll
+#else
+#pragma nounroll
+#endif
+          for (uint32_t k = 0; k < 4u; ++k) {
+            const uint32_t pw = k == 0u ? b[0] : k == 1u ? b[1] : k == 2u ? b[2] : b[3];
+            const bool o = k == 0u ? out[0] : k == 1u ? out[1] : k == 2u ? out[2] : out[3];
+            one_ray_lat(4u * q + k, pw, o, ek);
+          }
+        } else {
 #if RTHX_ROUND_UNROLL
 #pragma unroll
 #else
@@ -631,6 +715,7 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
           }
           if (in) one_ray(r, true, pw, ek);
         }
+        }
       }
     }
     };
@@ -643,6 +728,7 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
       (void)vrect;
       rounds(EmitKind<kEmitAny>{});
     }
+    if constexpr (LATRAY) tallied = tid == 0 ? re - rb : 0u;  // (the lost rays are off s_tallied already)
   } else if constexpr (MLAT) {
     // Layered / lattice domains.  Rays walk many coarse boxes and their walk
     // lengths differ widely, so a lane whose ray ended takes the next one at
