@@ -272,10 +272,26 @@ int rthx_result_copy_F(const rthx_result* res, int64_t* row_ptr, int32_t* cols, 
  * matrix without a host transpose (parallelRayTracing.jl:154-158):
  * colptr[N+1], rowval[nnz] (each column's rows ascending) and nzval[nnz],
  * indices counted from index_base (0, or 1 for Julia).  One-device results
- * are transposed on the device (radix sort of (column, row) keys); several
- * devices' results on the host.  Any pointer may be NULL. */
+ * are transposed on the device from the counts where they lie (the stable
+ * radix sort by column of rthx_csr_transpose; no sort library); several
+ * devices' results on the host.  Any pointer may be NULL.  nnz >= 2^31 on
+ * one device: RTHX_ERANGE. */
 int rthx_result_copy_F_csc(const rthx_result* res, int32_t index_base, int64_t* colptr, int64_t* rowval,
                            double* nzval);
+
+/* The transpose of a CSR matrix, on the device: the primitive
+ * behind rthx_result_copy_F_csc and the sparse GERT operators.  Host arrays
+ * in and out: row_ptr[n_rows + 1] (row_ptr[0] = 0, monotone), cols[nnz] in
+ * [0, n_cols) in any order within a row, finite vals[nnz] (else
+ * RTHX_EINVAL); n_rows, n_cols or nnz >= 2^31: RTHX_ERANGE.  Writes the CSR
+ * of the transpose: t_row_ptr[n_cols + 1], and per column its entries in
+ * ascending row order, t_cols[nnz] (their rows) and t_vals[nnz]; duplicates
+ * of one (row, column) pair keep their input order.  The result is one fixed
+ * permutation: bit-reproducible.  device_ms (may be NULL): hipEvent time of
+ * the transpose kernels alone. */
+int rthx_csr_transpose(int32_t device, int64_t n_rows, int64_t n_cols, const int64_t* row_ptr,
+                       const int32_t* cols, const double* vals, int64_t* t_row_ptr, int32_t* t_cols,
+                       double* t_vals, double* device_ms);
 
 /* Pin (page-lock) caller memory for direct device DMA, e.g. the cols/counts
  * arrays a caller reuses across traces; unregister before freeing it. */
@@ -430,8 +446,9 @@ void rthx_smooth_destroy(rthx_smooth_result* res);
  * solved on the device by restarted GMRES (the reference's sparse branch:
  * GMRES(memory = 50), rtol = 1e-12, Krylov.jl's atol = sqrt(eps), :158-160;
  * its dense branch uses an LU solve, which GMRES matches within the stated
- * tolerance).  F may be given as host CSR, as a dense host matrix, or as a
- * device-resident dense smoothing result.
+ * tolerance).  F may be given as host CSR, as a dense host matrix, as a
+ * device-resident smoothing result (dense or sparse), or as a trace result's
+ * counts.
  * ------------------------------------------------------------------------ */
 typedef struct rthx_solve_args {
   int32_t device;
@@ -458,10 +475,21 @@ typedef struct rthx_solve_info {
 int rthx_solve_grey(const int64_t* row_ptr, const int32_t* cols, const double* vals, const double* dense,
                     int64_t n, const double* coeff, const double* h, const rthx_solve_args* args,
                     double* j_out, double* g_out, rthx_solve_info* info);
-/* F = a dense rthx_smooth_F result, already on the device. */
+/* F = an rthx_smooth_F result, already on the device: a dense one is read in
+ * place; a sparse one's device CSR is transposed on the device (once; F' is
+ * kept in the handle, whose own CSR stays as it is). */
 int rthx_solve_grey_smoothed(const rthx_smooth_result* F, const double* coeff, const double* h,
                              const rthx_solve_args* args, double* j_out, double* g_out,
                              rthx_solve_info* info);
+/* F = the matrix rthx_smooth_F_result reads: the leading n x n block of a
+ * trace result's F_raw (count / the whole row's tallied rays; n = N, or the
+ * number of surfaces for a surfaces-only solve), transposed on the device
+ * from the counts where they lie.  The result must be a single-device trace
+ * on args->device of every row < n (emitter_begin 0, stride 1), else
+ * RTHX_EINVAL; without a trace RTHX_ESTATE; a pending RTHX_FLAG_ASYNC trace
+ * is completed first. */
+int rthx_solve_grey_result(const rthx_result* counts, int64_t n, const double* coeff, const double* h,
+                           const rthx_solve_args* args, double* j_out, double* g_out, rthx_solve_info* info);
 
 /* ------------------------------------------------------------------------
  * Spectral GERT solve (equilibriumSpectral2D!, equilibriumSurfacesSpectral3D!;
@@ -485,7 +513,7 @@ typedef struct rthx_spectral_band { /* one F_k; exactly one form is non-NULL */
   const int32_t* cols;
   const double* vals;
   const double* dense;                /* host dense, row-major n*n */
-  const rthx_smooth_result* smoothed; /* dense, already on the device */
+  const rthx_smooth_result* smoothed; /* dense or sparse, already on the device */
 } rthx_spectral_band;
 
 typedef struct rthx_spectral_args {

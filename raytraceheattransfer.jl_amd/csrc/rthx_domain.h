@@ -81,9 +81,10 @@ struct rthx_result {
   rthx::DevBuf acc_off, acc_cols, acc_cnt, acc_len, acc_mark, acc_totals, acc_err;
   hipEvent_t acc_ev[2] = {nullptr, nullptr};  // around the last accumulate's kernels
   double acc_ms = 0.0;                        // their device time (rthx_result_accumulate_ms)
-  // rthx_result_copy_F_csc: radix-sort keys / counts (double-buffered), the
-  // sort's scratch, row sums, and the CSC arrays before their host copy
-  rthx::DevBuf csc_keys[2], csc_vals[2], csc_tmp, csc_rowsum, csc_colptr, csc_rowval, csc_nz;
+  // rthx_result_copy_F_csc: the transpose's scratch block (rthx_transpose_plan.h),
+  // the rows' tallied rays, starts, lengths and offsets, and the CSC arrays
+  // before their host copy
+  rthx::DevBuf csc_scratch, csc_rowsum, csc_src, csc_len, csc_off, csc_colptr, csc_rowval, csc_nz;
   bool valid = false;
   bool host_row_off = false;
   int64_t N = 0, R = 0, n_rows = 0, begin = 0, stride = 1, split = 1;
@@ -119,7 +120,7 @@ struct rthx_result {
       if (e) (void)hipEventDestroy(e);
     rthx::DevBuf* all[] = {&stage_cols, &stage_cnt, &row_nnz,  &row_tallied, &row_off,  &totals, &cols,
                      &cnt,        &dense,     &rec_ids,  &rec_ok,      &rec_orig, &rec_end, &lb_status, &lb_totals, &fvals, &arrive,
-                     &csc_keys[0], &csc_keys[1], &csc_vals[0], &csc_vals[1], &csc_tmp, &csc_rowsum, &csc_colptr,
+                     &csc_scratch, &csc_rowsum, &csc_src, &csc_len, &csc_off, &csc_colptr,
                      &csc_rowval, &csc_nz, &acc_off, &acc_cols, &acc_cnt, &acc_len, &acc_mark, &acc_totals, &acc_err};
     for (rthx::DevBuf* b : all) b->release();
     h_cols.release();

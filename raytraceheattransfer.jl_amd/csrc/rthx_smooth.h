@@ -8,8 +8,11 @@
 
 #include "rthx_common.h"
 
-// The smoothing result handle (opaque in include/rthx.h).  The solver
-// (rthx_solve.cpp) reads a dense result in place.
+// The smoothing result handle (opaque in include/rthx.h).  The solvers
+// (rthx_solve.cpp, rthx_spectral.cpp) read a dense result in place; of a
+// sparse one they read F' (trp / tci / tv), formed on the device on first use
+// (rthx_transpose.h smooth_transposed) and kept here.  rp / ci / F stay as
+// they are for rthx_smooth_copy_csr.
 struct rthx_smooth_result {
   int device = -1;
   hipStream_t stream = nullptr;
@@ -18,12 +21,17 @@ struct rthx_smooth_result {
   rthx::DevBuf F;           // dense result (n*n, row-major) or sparse values
   rthx::DevBuf rp, ci;      // sparse pattern
   int64_t nnz = 0;
+  rthx::DevBuf trp, tci, tv;  // F' as CSR (sparse results)
+  bool have_t = false;
   rthx_smooth_info info{};
   ~rthx_smooth_result() {
     if (device >= 0) (void)hipSetDevice(device);
     F.release();
     rp.release();
     ci.release();  // (stream: the device's shared stream)
+    trp.release();
+    tci.release();
+    tv.release();
   }
 };
 

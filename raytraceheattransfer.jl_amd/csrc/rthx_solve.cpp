@@ -18,8 +18,10 @@
 #include <vector>
 
 #include "rthx_common.h"
+#include "rthx_domain.h"
 #include "rthx_smooth.h"
 #include "rthx_solve.h"
+#include "rthx_transpose.h"
 
 using rthx::DevBuf;
 using rthx::fail;
@@ -263,17 +265,48 @@ RTHX_EXPORT int rthx_solve_grey_smoothed(const rthx_smooth_result* F, const doub
                                          rthx_solve_info* info) {
   const double t0 = now_ms();
   if (!F) return fail(RTHX_EINVAL, "null smoothing result");
-  if (!F->dense) return fail(RTHX_ESTATE, "sparse smoothing result: copy it (rthx_smooth_copy_csr) and use rthx_solve_grey");
   STRY(check_args(F->n, coeff, h, args, j_out, g_out));
   if (args->device != F->device) return fail(RTHX_EINVAL, "args.device differs from the result's device");
   HIP_TRY(hipSetDevice(F->device), "hipSetDevice");
   Solver S;
   S.n = F->n;
   HIP_TRY(rthx::device_stream(F->device, &S.s), "hipStreamCreate");
-  HIP_TRY(S.part.reserve((size_t)rthx::gs::part_doubles(S.n) * 8), "hipMalloc");
-  S.op.dense = true;
   S.op.n = S.n;
-  S.op.F = F->F.as<double>();
-  S.op.part = S.part.as<double>();
+  if (F->dense) {
+    HIP_TRY(S.part.reserve((size_t)rthx::gs::part_doubles(S.n) * 8), "hipMalloc");
+    S.op.dense = true;
+    S.op.F = F->F.as<double>();
+    S.op.part = S.part.as<double>();
+  } else {  // F' from the handle's device CSR (formed once, kept in the handle)
+    S.op.dense = false;
+    STRY(rthx::tp::smooth_transposed(F, S.s, &S.op.rp, &S.op.ci, &S.op.v));
+  }
+  return run(S, coeff, h, args, j_out, g_out, info, t0);
+}
+
+RTHX_EXPORT int rthx_solve_grey_result(const rthx_result* counts, int64_t n, const double* coeff, const double* h,
+                                       const rthx_solve_args* args, double* j_out, double* g_out,
+                                       rthx_solve_info* info) {
+  const double t0 = now_ms();
+  if (!counts) return fail(RTHX_EINVAL, "null result");
+  STRY(rthx::result_ready(counts));  // (RTHX_ESTATE without a trace; completes a pending one)
+  STRY(check_args(n, coeff, h, args, j_out, g_out));
+  if (!counts->parts.empty() || counts->device < 0)
+    return fail(RTHX_EINVAL, "rthx_solve_grey_result needs a single-device result");
+  if (counts->begin != 0 || counts->stride != 1 || n > counts->n_rows || n > counts->N)
+    return fail(RTHX_EINVAL, "rthx_solve_grey_result needs a trace of every emitter row below n");
+  if (args->device != counts->device) return fail(RTHX_EINVAL, "args.device differs from the result's device");
+  if (counts->R < 1) return fail(RTHX_EINVAL, "a trace with R = 0 rays per emitter has no F_raw");
+  HIP_TRY(hipSetDevice(counts->device), "hipSetDevice");
+  Solver S;
+  S.n = n;
+  HIP_TRY(rthx::device_stream(counts->device, &S.s), "hipStreamCreate");
+  rthx::tp::Transposed Ft;
+  STRY(rthx::tp::transpose_result_block(counts, n, S.s, Ft));
+  S.op.dense = false;
+  S.op.n = n;
+  S.op.rp = Ft.rp.as<int64_t>();
+  S.op.ci = Ft.ci.as<int32_t>();
+  S.op.v = Ft.v.as<double>();
   return run(S, coeff, h, args, j_out, g_out, info, t0);
 }

@@ -20,6 +20,7 @@
 #include "rthx_smooth.h"
 #include "rthx_solve.h"
 #include "rthx_spectral.h"
+#include "rthx_transpose.h"
 
 using rthx::DevBuf;
 using rthx::fail;
@@ -72,7 +73,6 @@ int check_bands(const rthx_spectral_band* F, int32_t n_mats, int64_t n, int32_t 
     const int forms = (sparse ? 1 : 0) + (F[k].dense ? 1 : 0) + (F[k].smoothed ? 1 : 0);
     if (forms != 1) return fail(RTHX_EINVAL, "band " + std::to_string(k) + ": exactly one matrix form expected");
     if (F[k].smoothed) {
-      if (!F[k].smoothed->dense) return fail(RTHX_EINVAL, "sparse smoothing result: copy it (rthx_smooth_copy_csr)");
       if (F[k].smoothed->device != device) return fail(RTHX_EINVAL, "smoothing result lies on another device");
       if (F[k].smoothed->n != n) return fail(RTHX_EINVAL, "smoothing result of another size");
     } else if (F[k].dense) {
@@ -120,7 +120,10 @@ struct Operator {
     op.n_mats = n_mats;
     for (int k = 0; k < n_mats; ++k) {
       void* p = nullptr;
-      if (F[k].smoothed) {
+      if (F[k].smoothed && !F[k].smoothed->dense) {  // F' from the handle's device CSR
+        STRY(rthx::tp::smooth_transposed(F[k].smoothed, s, &host[k].rp, &host[k].ci, &host[k].v));
+        op.any_sparse = true;
+      } else if (F[k].smoothed) {
         host[k].F = F[k].smoothed->F.as<double>();
         op.any_dense = true;
       } else if (F[k].dense) {

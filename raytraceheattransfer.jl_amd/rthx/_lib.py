@@ -102,6 +102,13 @@ def load(path: Optional[str] = None) -> C.CDLL:
                                     C.POINTER(abi.SolveArgs), dp, dp, C.POINTER(abi.SolveInfo)]
     lib.rthx_solve_grey_smoothed.argtypes = [C.c_void_p, dp, dp, C.POINTER(abi.SolveArgs), dp, dp,
                                              C.POINTER(abi.SolveInfo)]
+    if hasattr(lib, "rthx_solve_grey_result"):  # (older A/B variant libraries lack it)
+        lib.rthx_solve_grey_result.argtypes = [C.c_void_p, C.c_int64, dp, dp, C.POINTER(abi.SolveArgs), dp, dp,
+                                               C.POINTER(abi.SolveInfo)]
+    if hasattr(lib, "rthx_csr_transpose"):  # (older A/B variant libraries lack it)
+        lib.rthx_csr_transpose.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_int32), dp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), dp,
+                                           dp]
     pb = C.POINTER(abi.SpectralBand)
     lib.rthx_solve_spectral.argtypes = [pb, C.c_int32, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, dp,
                                         C.POINTER(abi.SpectralArgs), dp, dp, dp, dp, C.POINTER(abi.SpectralInfo)]

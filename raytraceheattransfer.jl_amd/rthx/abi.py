@@ -304,6 +304,7 @@ EXPORTED_SYMBOLS = (
     "rthx_result_copy_rays",
     "rthx_result_copy_F",
     "rthx_result_copy_F_csc",
+    "rthx_csr_transpose",
     "rthx_result_get_device_csr",
     "rthx_result_copy_csr_device",
     "rthx_merge_row_shards",
@@ -320,6 +321,7 @@ EXPORTED_SYMBOLS = (
     "rthx_smooth_destroy",
     "rthx_solve_grey",
     "rthx_solve_grey_smoothed",
+    "rthx_solve_grey_result",
     "rthx_solve_spectral",
     "rthx_spectral_apply",
     "rthx_spectral_fractions",

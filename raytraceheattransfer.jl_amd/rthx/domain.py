@@ -351,10 +351,17 @@ class RayTracingDomain2D:
     def F_raw(self, value):
         self._F_raw = value
         self._F_raw_lazy = None
+        self._F_raw_device = None
 
-    def _set_F_raw_lazy(self, thunk) -> None:
+    def _set_F_raw_lazy(self, thunk, device_F=None) -> None:
         self._F_raw = None
         self._F_raw_lazy = thunk
+        self._F_raw_device = device_F
+
+    def F_raw_device(self):
+        """The device-resident F_raw of the last lazy trace (a DeviceF, or a
+        list of one per bin), or None; rthx.equilibrium solves from it."""
+        return getattr(self, "_F_raw_device", None)
 
     @property
     def F_smooth(self):
@@ -385,6 +392,12 @@ class RayTracingDomain2D:
         """The device-resident dense F_smooth handle, or None."""
         dev = getattr(self, "_F_smooth_device", None)
         return dev[1] if dev is not None and dev[1].dense else None
+
+    def F_smooth_handle(self):
+        """The device-resident F_smooth handle, dense or sparse, or None (the
+        GERT solves read either form in place)."""
+        dev = getattr(self, "_F_smooth_device", None)
+        return dev[1] if dev is not None else None
 
     @property
     def num_surfaces(self) -> int:

@@ -59,7 +59,12 @@ def populate_workspace(dom, spectral_bin: int = 1) -> dict:
 
 
 def _solve(F, coeff, h, device, info, rtol=1e-12, atol=math.sqrt(np.finfo(np.float64).eps), memory=50,
-           handle=None):
+           handle=None, result=None):
+    """(I - Diagonal(coeff) F') j = h and g = F' j on the device.  F: a
+    SmoothHandle (`handle`, dense or sparse, read in place), a trace result's
+    device counts (`result`: the leading len(h) block of its F_raw,
+    rthx_solve_grey_result), a scipy sparse matrix or a dense array.  `info`
+    receives rthx_solve_info and ``F_form``: which of these was passed."""
     lib = load()
     n = len(h)
     a = abi.SolveArgs()
@@ -71,9 +76,15 @@ def _solve(F, coeff, h, device, info, rtol=1e-12, atol=math.sqrt(np.finfo(np.flo
     inf = abi.SolveInfo()
     dp = C.c_double
     if handle is not None:
+        form = "smoothed_dense" if handle.dense else "smoothed_sparse"
         check(lib.rthx_solve_grey_smoothed(handle.handle, abi.ptr(co, dp), abi.ptr(hh, dp), C.byref(a),
                                            abi.ptr(j, dp), abi.ptr(g, dp), C.byref(inf)))
+    elif result is not None:
+        form = "result"
+        check(lib.rthx_solve_grey_result(result.handle, n, abi.ptr(co, dp), abi.ptr(hh, dp), C.byref(a),
+                                         abi.ptr(j, dp), abi.ptr(g, dp), C.byref(inf)))
     elif sp.issparse(F):
+        form = "host_csr"
         Fc = F.tocsr()
         rp = np.ascontiguousarray(Fc.indptr, dtype=np.int64)
         ci = np.ascontiguousarray(Fc.indices, dtype=np.int32)
@@ -82,11 +93,13 @@ def _solve(F, coeff, h, device, info, rtol=1e-12, atol=math.sqrt(np.finfo(np.flo
                                   abi.ptr(co, dp), abi.ptr(hh, dp), C.byref(a), abi.ptr(j, dp), abi.ptr(g, dp),
                                   C.byref(inf)))
     else:
+        form = "host_dense"
         Fd = np.ascontiguousarray(F, dtype=np.float64)
         check(lib.rthx_solve_grey(None, None, None, abi.ptr(Fd, dp), n, abi.ptr(co, dp), abi.ptr(hh, dp),
                                   C.byref(a), abi.ptr(j, dp), abi.ptr(g, dp), C.byref(inf)))
     if info is not None:
         info.update(inf.as_dict())
+        info["F_form"] = form
     return j, g
 
 
@@ -95,7 +108,12 @@ def equilibrium_grey(dom, F, spectral_bin: int = 1, device: int = 0, verbose: bo
     """equilibriumGrey2D! (equilibriumGrey2D.jl:80-211).  Writes T_w, j_w,
     g_a_w, e_w, r_w, g_w, q_w, i_w (walls) and T_g, j_g, ... (volumes) into the
     fine faces, sets dom.energy_error, and returns (T, j, Abs, r) in global
-    element order."""
+    element order.  F: None (dom.F_smooth, read in place on the device when it
+    lives there, dense or sparse), a DeviceF (the lazy F_raw of
+    exchange_ray_tracing: solved from its device counts), a scipy sparse
+    matrix or a dense array."""
+    from .exchange import DeviceF
+
     ws = populate_workspace(dom, spectral_bin)
     ns = len(ws["Area"])
     nv = len(ws["Volume"])
@@ -125,22 +143,27 @@ def equilibrium_grey(dom, F, spectral_bin: int = 1, device: int = 0, verbose: bo
     coeff = np.where(Q_known == 1, 1.0, b)
     Fm = F
     handle = None
+    result = None
     dev = getattr(dom, "_F_smooth_device", None)
     if F is None:  # dom.F_smooth: read in place on the device when it lives there
-        if dom.F_smooth_device() is not None:
-            handle = dom.F_smooth_device()
+        if dom.F_smooth_handle() is not None:
+            handle = dom.F_smooth_handle()
         else:
             F = Fm = dom.F_smooth
     if handle is not None:
         pass
-    elif dev is not None and dev[0] is F and dev[1].dense:
+    elif isinstance(F, DeviceF):  # F_raw's counts, where the trace left them
+        result, Fm = F.res, None
+        device = result.device
+    elif dev is not None and dev[0] is F:
         handle = dev[1]
     elif sp.issparse(F):
         Fm = F.tocsr()[:n, :n]
     else:
         Fm = np.asarray(F)[:n, :n]
     solve_info = {} if info is None else info
-    j, g = _solve(Fm, coeff, h, device, solve_info, handle=handle)
+    j, g = _solve(Fm, coeff, h, device, solve_info, handle=handle, result=result)
+    dom.last_solve_info = solve_info  # (F_form: which form of F the solve was handed)
     if verbose:
         print(f"GMRES: {solve_info['iterations']} iterations in {solve_info['cycles']} cycles, "
               f"residual {solve_info['residual']:.3e} (tolerance {solve_info['tolerance']:.3e})")
@@ -284,8 +307,9 @@ def _check_band_limits(limits, n_bins: int) -> np.ndarray:
 
 
 def _band_struct(F, n: int, handle, keep: list) -> abi.SpectralBand:
-    """One rthx_spectral_band from a SmoothHandle, a scipy sparse matrix or a
-    dense array (its leading n x n block); `keep` holds the arrays alive."""
+    """One rthx_spectral_band from a SmoothHandle (dense or sparse), a scipy
+    sparse matrix or a dense array (its leading n x n block); `keep` holds
+    the arrays alive."""
     band = abi.SpectralBand()
     if handle is not None:
         band.smoothed = handle.handle
@@ -377,13 +401,13 @@ def equilibrium_spectral(dom, F=None, device: int = 0, max_iters: int = 1000, co
     q_in = np.concatenate([wss[0]["qw"], wss[0]["qg"]])
     handles = None
     if F is None:
-        if dom.F_smooth_device() is not None:
-            handles = [dom.F_smooth_device()]
+        if dom.F_smooth_handle() is not None:
+            handles = [dom.F_smooth_handle()]
         else:
             F = dom.F_smooth
     else:
         dev = getattr(dom, "_F_smooth_device", None)
-        if dev is not None and dev[0] is F and dev[1].dense:
+        if dev is not None and dev[0] is F:
             handles = [dev[1]]
     if handles is not None:
         F = [None]

@@ -117,6 +117,7 @@ def release_device_results(dom) -> None:
     for r in getattr(dom, "_trace_results", {}).values():
         r.close()
     dom._trace_results = {}
+    dom._F_raw_device = None
 
 
 def _default_backend():
@@ -289,7 +290,7 @@ def exchange_ray_tracing(dom, rays_tot: int, nudge: float, verbose: bool, rec=No
     ns = dom.num_surfaces
     dom.rays_per_emitter = rpe
     if lazy:
-        dom._set_F_raw_lazy(lambda: materialize_F_raw(F_raw, ns, dom.surfaces_only))
+        dom._set_F_raw_lazy(lambda: materialize_F_raw(F_raw, ns, dom.surfaces_only), F_raw)
         return None
     if dom.surfaces_only:
         if isinstance(F_raw, list):

@@ -33,7 +33,8 @@ def get_w(dom, spectral_bin: int = 1) -> np.ndarray:
 
 
 class SmoothHandle:
-    """A device-resident rthx_smooth_result (kept for rthx_solve_grey_smoothed)."""
+    """A device-resident rthx_smooth_result, dense or sparse (kept for
+    rthx_solve_grey_smoothed and rthx_solve_spectral)."""
 
     def __init__(self, lib, h, device: int, dense: bool, inf=None):
         self._lib, self.handle, self.device, self.dense = lib, h, device, dense
@@ -143,6 +144,30 @@ def smooth_F(F_raw, w, num_surfaces: int, max_iters: int = 1000, smooth_surfaces
         return out, SmoothHandle(lib, h, device, bool(inf.dense))
     lib.rthx_smooth_destroy(h)
     return out
+
+
+def csr_transpose(A, device: int = 0, info: Optional[dict] = None) -> sp.csr_matrix:
+    """The transpose of a scipy CSR matrix as CSR, formed on the device
+    (rthx_csr_transpose): every row of the result in ascending column order,
+    duplicates of one (row, column) pair in their input order.  ``info``
+    (optional dict) receives ``device_ms``, the transpose kernels' time."""
+    lib = load()
+    A = A if sp.isspmatrix_csr(A) else sp.csr_matrix(A)
+    n_rows, n_cols = A.shape
+    rp = np.ascontiguousarray(A.indptr, dtype=np.int64)
+    ci = np.ascontiguousarray(A.indices, dtype=np.int32)
+    vv = np.ascontiguousarray(A.data, dtype=np.float64)
+    nnz = int(rp[-1])
+    trp = np.empty(n_cols + 1, dtype=np.int64)
+    tci = np.empty(max(nnz, 1), dtype=np.int32)
+    tv = np.empty(max(nnz, 1))
+    ms = C.c_double(0.0)
+    check(lib.rthx_csr_transpose(device, n_rows, n_cols, abi.ptr(rp, C.c_int64), abi.ptr(ci, C.c_int32),
+                                 abi.ptr(vv, C.c_double), abi.ptr(trp, C.c_int64), abi.ptr(tci, C.c_int32),
+                                 abi.ptr(tv, C.c_double), C.byref(ms)))
+    if info is not None:
+        info["device_ms"] = ms.value
+    return sp.csr_matrix((tv[:nnz], tci[:nnz], trp), shape=(n_cols, n_rows))
 
 
 def result_device(res) -> int:

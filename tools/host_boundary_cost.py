@@ -80,8 +80,8 @@ def main():
 
 
 def gpu_leg(reps):
-    """The same F_raw in CSC from the device (rthx_result_copy_F_csc: keys,
-    radix sort and CSC arrays on the GPU, then three D2H copies) into
+    """The same F_raw in CSC from the device (rthx_result_copy_F_csc: the
+    transpose kernels of DESIGN.md 7h on the GPU, then three D2H copies) into
     page-locked caller arrays, at C2 with 1e8 rays."""
     import ctypes as C
 
