@@ -61,6 +61,7 @@ constexpr int kSc1 = 16;
 // shards unchanged (profiles/round5/ab/tables_global.log).  0: LDS (A/B).
 #define RTHX_GTAB 1
 #endif
+typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 #ifndef RTHX_REFILL_Q
 #define RTHX_REFILL_Q 40  // MLAT kernels: idle lanes before the ends are resolved and the queue refills (C5 at 1e9 rays, band 0 / 4, with walk_layers' fast loop: 24 53.0 / 34.0 ms, 32 49.8 / 32.9, 40 50.2 / 31.2, 48 51.8 / 30.7, 56 59.6 / 32.1; at 1e8: 24 8.65 / 6.45, 40 8.50 / 6.08, 48 9.04 / 6.26)
 #endif
@@ -423,7 +424,7 @@ template <bool UNIFORM, int TALLY, bool FAITHFUL, bool SINGLE, bool REC, bool SP
 __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_exchange_kernel(const DevDomain* __restrict__ Dp,
                                                                      TraceParams P, TallyParams T,
                                                                      RecordParams rec) {
-  extern __shared__ uint32_t hist[];
+  extern __shared__ __attribute__((aligned(16))) uint32_t hist[];  // (zeroed and handed off as uint4s)
   const DevDomain& D = *Dp;
   __shared__ uint32_t wave_sum[kMaxTraceThreads / 64];
   __shared__ uint32_t s_tallied;
@@ -477,13 +478,32 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
                               : (SPLIT ? (r_begin + chunk < P.R ? r_begin + chunk : P.R) : P.R);
   const int64_t g = P.g_begin + slot * P.g_stride;
   constexpr bool PACK16 = TALLY == kTallyU16, HASH = TALLY == kTallyHash;
+  // The uniform LAT ray (one_ray_lat below): its rows count their lost rays
+  // off s_tallied and add the row's ray count once.
+  constexpr bool LATRAY = SINGLE && CL != 0 && AXIS && UNIFORM && !RBASE;
   const int64_t n_words = HASH ? 2 * (int64_t)T.hash_cap + T.bm_words : PACK16 ? (T.n_emitters + 1) / 2 : T.n_emitters;
 
   const int nthr = (int)blockDim.x;  // 256, 512 or 1024 (launch_trace_t)
-  // (split histogram kernels: through the 16-byte padding too, which the
-  // slab hand-off moves as whole uint4s; the host sizes LDS for it)
-  const int64_t z_words = SPLIT && !HASH ? (n_words + 3) & ~int64_t(3) : n_words;
-  for (int64_t w = tid; w < z_words; w += nthr) hist[w] = 0u;
+  // The row's tally zeroed by 16-byte LDS stores (with the lane-0 add of the
+  // ray count below: C2 kernel 0.6375 -> 0.6240 ms, DESIGN.md §3,
+  // profiles/round11/ab/parts_B_C.log).  Histograms: whole uint4s, through
+  // the 16-byte padding that the host allocates (and the slab hand-off of
+  // split rows moves); a hash table and its bitmap end on any word: a scalar
+  // tail.  32-bit indices: LDS.
+  // (The SINGLE instances that read a ray base keep the word loop: with the
+  // uint4 loop their ray loop spills 71 scalar registers instead of 57 and
+  // the base-1001 launch measured 1.4 % slower,
+  // profiles/round11/ab/regressions_first.log.)
+  if constexpr (SINGLE && RBASE) {
+    const int64_t z_words = SPLIT && !HASH ? (n_words + 3) & ~int64_t(3) : n_words;  // (the slabs' padding too)
+    for (int64_t w = tid; w < z_words; w += nthr) hist[w] = 0u;
+  } else {
+    const uint32_t zw = (uint32_t)n_words;
+    const uint32_t z4 = HASH ? zw >> 2 : (zw + 3u) >> 2;
+    u4 RTHX_LDS* h4 = (u4 RTHX_LDS*)(uint32_t RTHX_LDS*)hist;
+    for (uint32_t c = (uint32_t)tid; c < z4; c += (uint32_t)nthr) h4[c] = u4{0u, 0u, 0u, 0u};
+    if (HASH && 4u * z4 + (uint32_t)tid < zw) hist[4u * z4 + (uint32_t)tid] = 0u;
+  }
   // CLDS: the coarse mesh behind the histogram (T.cl_offset bytes in), and
   // this bin's coarse betas
   char RTHX_LDS* cl_base = (char RTHX_LDS*)hist + T.cl_offset;
@@ -612,7 +632,6 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
     // live in the loop the fast body's registers no longer fit 64 VGPRs, and
     // the spilled form measured 1 % slower than segment_lat there,
     // profiles/round9/ab/regressions_first.log.)
-    constexpr bool LATRAY = CLDS && AXIS && UNIFORM && !RBASE;
     const bool lat_identity = LATRAY && __builtin_amdgcn_readfirstlane(D.lat.identity) != 0;
     auto one_ray_lat = [&](uint32_t r, uint32_t pw, bool cold0, auto ek) {
       constexpr int EK = decltype(ek)::value;
@@ -728,7 +747,6 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
       (void)vrect;
       rounds(EmitKind<kEmitAny>{});
     }
-    if constexpr (LATRAY) tallied = tid == 0 ? re - rb : 0u;  // (the lost rays are off s_tallied already)
   } else if constexpr (MLAT) {
     // Layered / lattice domains.  Rays walk many coarse boxes and their walk
     // lengths differ widely, so a lane whose ray ended takes the next one at
@@ -915,9 +933,14 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
       }
     }
   }
-  // wave reduce the tallied count, one LDS atomic per wave
-  for (int off = 32; off > 0; off >>= 1) tallied += __shfl_xor(tallied, off);
-  if (lane_id() == 0) atomicAdd(&s_tallied, tallied);
+  if constexpr (LATRAY) {
+    // no lane counted (the lost rays are off s_tallied already): lane 0 of the workgroup adds the rays of the row (or part)
+    if (tid == 0) atomicAdd(&s_tallied, (uint32_t)(r_end > r_begin ? r_end - r_begin : 0));
+  } else {
+    // wave reduce the tallied count, one LDS atomic per wave
+    for (int off = 32; off > 0; off >>= 1) tallied += __shfl_xor(tallied, off);
+    if (lane_id() == 0) atomicAdd(&s_tallied, tallied);
+  }
   __syncthreads();
 
   // direct CSR (single-polygon domains, unsplit): the row's offset is the sum
@@ -1007,7 +1030,6 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
   // four slabs in flight.  It resets the counter, so the counters are zero
   // between launches.
   __shared__ uint32_t s_merge;  // bit 0: this part arrived last; bit 1: a packed pair overflowed 16 bits
-  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
   const int64_t wstride = (n_words + 3) & ~int64_t(3);  // slab words (whole uint4s)
   const uint32_t* slabs = tail ? T.dense + (size_t)trow * parts * (size_t)wstride : nullptr;
   if constexpr (SPLIT && !HASH) {

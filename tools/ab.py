@@ -29,6 +29,7 @@ def open_lib(path):
     lib.rthx_domain_create.argtypes = [C.POINTER(abi.DomainDesc), C.c_int32, C.POINTER(C.c_void_p)]
     lib.rthx_result_create.argtypes = [C.POINTER(C.c_void_p)]
     lib.rthx_trace_exchange.argtypes = [C.c_void_p, C.POINTER(abi.TraceArgs), C.c_void_p]
+    lib.rthx_trace_exchange_rays.argtypes = [C.c_void_p, C.POINTER(abi.TraceArgs), C.c_int64, C.c_void_p]
     lib.rthx_result_get_info.argtypes = [C.c_void_p, C.POINTER(abi.ResultInfo)]
     return lib
 
@@ -43,6 +44,8 @@ def main():
     ap.add_argument("--c5-bin", type=int, default=-1, help="time one band of the C5 greenhouse instead of C2")
     ap.add_argument("--stride", type=int, default=1,
                     help="rank 0's rows of a W-way row shard (rows 0, W, 2W, ...; --rays stays the whole job's)")
+    ap.add_argument("--ray-base", type=int, default=0,
+                    help="first ray id of every row (rthx_trace_exchange_rays: the instances that read a ray base)")
     ap.add_argument("--env", default="",
                     help="NAME=v1,v2,...: every library is also timed with each value of that knob "
                          "(RTHX_DEV_KNOBS is set; 'auto' leaves the knob unset)")
@@ -90,6 +93,11 @@ def main():
         else:
             os.environ[knob] = v
 
+    def trace(lib, h, r):
+        if args.ray_base:
+            return lib.rthx_trace_exchange_rays(h, C.byref(targs), args.ray_base, r)
+        return lib.rthx_trace_exchange(h, C.byref(targs), r)
+
     runs = []
     for p in args.libs:
         lib = open_lib(p)
@@ -99,7 +107,7 @@ def main():
             assert lib.rthx_domain_create(C.byref(flat.desc), 0, C.byref(h)) == 0, lib.rthx_last_error()
             assert lib.rthx_result_create(C.byref(r)) == 0
             for _ in range(2):
-                assert lib.rthx_trace_exchange(h, C.byref(targs), r) == 0, lib.rthx_last_error()
+                assert trace(lib, h, r) == 0, lib.rthx_last_error()
             tag = os.path.basename(os.path.dirname(p)) or p
             label = f" [{v}]" if knob == "sets" else (f" {knob}={v}" if knob else "")
             runs.append((tag + label, lib, h, r, [], v))
@@ -107,7 +115,7 @@ def main():
         for p, lib, h, r, ts, v in runs:
             set_knob(v)
             for _ in range(args.steps):
-                assert lib.rthx_trace_exchange(h, C.byref(targs), r) == 0
+                assert trace(lib, h, r) == 0
                 inf = abi.ResultInfo()
                 lib.rthx_result_get_info(r, C.byref(inf))
                 ts.append(inf.trace_ms + (inf.pack_ms if args.with_pack else 0.0))
