@@ -15,11 +15,8 @@
 #else
 #define RTHX_GLOBAL
 #endif
-
-// 1: keep the Philox key schedule out of loop-invariant SGPRs (A/B knob)
-#ifndef RTHX_PHILOX_OPAQUE_KEY
-#define RTHX_PHILOX_OPAQUE_KEY 1
-#endif
+// LDS pointers (ds_read / ds_write instead of flat accesses).
+#define RTHX_LDS __attribute__((address_space(3)))
 
 namespace rthx {
 
@@ -198,11 +195,10 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
 
 template <int ROUNDS = 10>
 __device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#if RTHX_PHILOX_OPAQUE_KEY
   // Opaque key: the 20 round keys are formed in each block (scalar adds)
-  // instead of being hoisted into 20 SGPRs held across the whole ray loop.
+  // instead of being hoisted into 20 SGPRs held across the whole ray loop
+  // (no slower than hoisted keys, profiles/round5/ab/philox_opaque_key.log).
   __asm__ volatile("" : "+s"(k0), "+s"(k1));
-#endif
 #pragma unroll
   for (int i = 0; i < ROUNDS; ++i) {
     // one 32x32->64 multiply per product (v_mad_u64_u32) instead of mul_lo + mul_hi
@@ -1018,10 +1014,6 @@ __device__ __forceinline__ int segment(const DevDomain& D, const TraceParams& P,
 // reference's first hit in any candidate order -- found here by a guess
 // from the uniform spacing, corrected against the exact boundaries.
 // ---------------------------------------------------------------------------
-#ifndef RTHX_LDS
-#define RTHX_LDS __attribute__((address_space(3)))
-#endif
-
 // Index i with b[i] <= x < b[i+1], 0 <= i < n, or -1.  The guess from the
 // uniform spacing is exact except for x within rounding of a boundary; the
 // walk that corrects it runs only then (for every lane of a wave only when
@@ -1202,11 +1194,6 @@ __device__ __forceinline__ int lattice_guess(double x, double x0, double inv, in
   return i;
 }
 
-// 0: the f_surf load of lat_ray_fast runs for every lane (A/B knob)
-#ifndef RTHX_LAT_SURF_MASKED
-#define RTHX_LAT_SURF_MASKED 1
-#endif
-
 // INSIDE: as segment_lat.  identity: LatticeLayout::identity (uniform).
 // Returns the absorber of a lane that is not cold.
 template <bool INSIDE>
@@ -1270,7 +1257,7 @@ __device__ __forceinline__ int lat_ray_fast(const DevDomain& D, double eta, cons
   // are clamped.  The load still runs for the wall lanes only: for every
   // lane it is 64 scattered L2 reads a ray)
   int surf = -1;
-  if (!RTHX_LAT_SURF_MASKED || wall) surf = ld_off32(D.f_surf, ((uint32_t)f << 4) + ((uint32_t)wl << 2));
+  if (wall) surf = ld_off32(D.f_surf, ((uint32_t)f << 4) + ((uint32_t)wl << 2));
   const int a = gas ? sc.n_surfaces + f : surf;
   r.cold = cold0 | lost | !hit | (wall & !(vx | vy)) | (a < 0);
   return a;
@@ -1300,10 +1287,6 @@ __device__ __forceinline__ int lat_ray_fixup(const DevDomain& D, const SingleCoa
 // read its record, walls and fine grid, read beta -- runs on LDS latency
 // instead of four dependent L2 round trips.
 // ---------------------------------------------------------------------------
-#ifndef RTHX_LDS
-#define RTHX_LDS __attribute__((address_space(3)))
-#endif
-
 // Copy of an object in LDS or global memory (the implicit copy constructor
 // takes a generic-address-space reference).
 template <class T>

@@ -12,7 +12,7 @@ namespace rthx {
 constexpr int kTraceThreads = 256;               // default workgroup: 4 waves of 64 per emitter row (slice)
 constexpr int kMaxTraceThreads = 1024;           // large-N rows (LDS-bound occupancy) use up to 16 waves
 constexpr size_t kMaxLdsBytes = 160 * 1024;      // gfx950 LDS per CU
-constexpr int64_t kStaticLdsBytes = 10240;      // the trace kernel's static LDS (emitter, coarse, tables, ...)
+constexpr int64_t kStaticLdsBytes = 10240;      // bound on the trace kernel's static LDS (emitter, coarse polygon, ...)
 constexpr size_t kMaxCoarseLdsBytes = 48 * 1024; // largest coarse mesh the CLDS kernels stage in LDS
 
 struct RecordParams {

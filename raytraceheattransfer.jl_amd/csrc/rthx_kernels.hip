@@ -1,19 +1,33 @@
 // rthx_kernels.hip — exchange-factor trace kernels for gfx950 (MI355X).
 //
 // trace_exchange_kernel: the per-emitter loop of computeExchangeFactorsBin
-//   (parallelRayTracing.jl:102-150).  A workgroup of 256 lanes traces the
-//   rays of one emitter row (or, SPLIT, one slice of a row) and tallies
+//   (parallelRayTracing.jl:102-150).  A workgroup of 256, 512 or 1024 lanes
+//   (launch_trace_t picks the size that keeps most waves resident) traces
+//   the rays of one emitter row (or, SPLIT, one slice of a row) and tallies
 //   absorbers into an LDS histogram -- the reference's Dict{Int,Int} row --
 //   with uint16 counters packed two per dword when a workgroup traces fewer
 //   than 65536 rays.  Unsplit rows are then compacted in ascending absorber
-//   order into a fixed-stride staging slot of min(N, R) entries (no global
-//   atomics, deterministic); split rows add their histogram into a dense
-//   per-row count buffer that row_compact_kernel compacts afterwards.
+//   order (no global atomics, deterministic) straight into the CSR at an
+//   offset found by a decoupled look-back over the launch's rows, or into a
+//   fixed-stride staging slot of min(N, R) entries.  Split rows: every part
+//   stores its histogram into its slab of the row in global memory, and the
+//   part that finishes last sums the slabs and writes the row as an unsplit
+//   row does.
 //   Large N (the packed histogram does not fit LDS): the row is an LDS hash
-//   table of (absorber, count) -- the Dict itself -- sorted in LDS at the end
-//   of the row; split rows' sorted parts are merged by part_merge_kernel.
+//   table of (absorber, count) -- the Dict itself -- put in order through an
+//   LDS bitmap or a sort at the end of the row; split rows' sorted parts are
+//   merged by part_merge_kernel.
+//   The body runs, in order: the row range, the zeroing of the tally, the
+//   staging of the LDS block behind it, the emitter set-up by lane 0, one of
+//   three ray loops (SINGLE group rounds, MLAT ray queue, ray regeneration),
+//   the sum of the tallied count, and a row writer (hash row; split hand-off
+//   and histogram row).
+// row_compact_kernel: serves only the 3D tracer, whose split rows add into a
+//   dense per-row count buffer (rthx_trace3d.cpp finish_staged, kMergeDense).
+// part_merge_kernel: merges the sorted part lists of a split hash row.
 // row_scan_kernel: exclusive scan of per-row nnz + lost-ray reductions.
-// csr_pack_kernel: copies every row's staging slot into the dense CSR arrays.
+// csr_pack_kernel: copies a staged launch's row slots into the dense CSR arrays.
+// counts_to_F_kernel: a CSR of counts into exchange factors (count / row sum).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -50,17 +64,6 @@ namespace rthx {
 #endif
 constexpr int kBufferRsrcWord3 = 0x00020000;
 constexpr int kSc1 = 16;
-#ifndef RTHX_ROUND_UNROLL
-#define RTHX_ROUND_UNROLL 1  // SINGLE group rounds: the four rays of a round unrolled (0: one body, the word picked by k)
-#endif
-#ifndef RTHX_GTAB
-// 1: the cos / log tables (and 1 / beta_uniform) read from the domain's
-// per-bin copy in global memory (L1 / L2) instead of LDS: 8 KB less LDS per
-// workgroup; C5 bands -1.2 % at 1e9 rays and -27 % at 1e8 (more of its
-// short-row workgroups fit a CU), C2 and C3 unchanged, the emulated strong
-// shards unchanged (profiles/round5/ab/tables_global.log).  0: LDS (A/B).
-#define RTHX_GTAB 1
-#endif
 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 #ifndef RTHX_REFILL_Q
 #define RTHX_REFILL_Q 40  // MLAT kernels: idle lanes before the ends are resolved and the queue refills (C5 at 1e9 rays, band 0 / 4, with walk_layers' fast loop: 24 53.0 / 34.0 ms, 32 49.8 / 32.9, 40 50.2 / 31.2, 48 51.8 / 30.7, 56 59.6 / 32.1; at 1e8: 24 8.65 / 6.45, 40 8.50 / 6.08, 48 9.04 / 6.26)
@@ -436,15 +439,9 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
   // SINGLE: the one coarse polygon and its fine grid, also in LDS, so that
   // its 16 doubles do not occupy SGPRs for the whole loop.
   __shared__ SingleCoarse s_single;
-#if RTHX_GTAB
-  // cos and log tables and inv_beta_uniform read from global memory (L1 / L2;
-  // the domain's per-bin copy): 8 KB less LDS per workgroup
+  // cos and log tables and inv_beta_uniform read from the domain's per-bin copy in global memory (L1 / L2), not
+  // LDS: C5 -1.2 % at 1e9 rays, -27 % at 1e8, C2 / C3 unchanged (profiles/round5/ab/tables_global.log)
   const double* const g_tab = (const double*)((const double RTHX_GLOBAL*)D.tables + (size_t)P.bin * kLdsTableDoubles);
-#define RTHX_TAB_PTR g_tab
-#else
-  __shared__ double s_tab[kLdsTableDoubles];  // cos and log tables, inv_beta_uniform (rthx_device.h)
-#define RTHX_TAB_PTR ((const double*)lds_opaque(&s_tab[0]))
-#endif
 
   // CL: what sits in LDS behind the row tally.  SINGLE: 1 = the lattice of
   // the one coarse rectangle (LAT).  Multi-polygon: 1 = the coarse mesh
@@ -455,7 +452,6 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
   // SPLIT: every row is `split` workgroups, part p tracing rays
   // [p chunk, (p+1) chunk).  32-bit: R < 2^32.
   const uint32_t bid = blockIdx.x;
-  constexpr bool tail = SPLIT;
   const uint32_t parts = SPLIT ? (uint32_t)T.split : 1u;
   const uint32_t trow = SPLIT ? bid / parts : bid;  // the row (slot)
   const uint32_t tpart = SPLIT ? bid - trow * parts : 0u;
@@ -538,10 +534,6 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
     double RTHX_LDS* cb = (double RTHX_LDS*)(cl_base + D.cl.off_beta);
     for (int i = tid; i < D.n_coarse; i += nthr) cb[i] = D.c_beta[(size_t)P.bin * D.n_coarse + i];
   }
-#if !RTHX_GTAB
-  if (!FAITHFUL)
-    for (int i = tid; i < kLdsTableDoubles; i += nthr) s_tab[i] = i < kTableDoubles ? D.tables[i] : P.inv_beta_uniform;
-#endif
   if (tid == 0) {
     s_tallied = 0u;
     s_next = (uint32_t)r_begin;
@@ -613,7 +605,7 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
       // Opaque LDS addresses: re-read the loop-invariant coarse record and cos
       // table at their point of use instead of hoisting ~40 values into VGPRs.
       const SingleCoarse RTHX_LDS* sc = lds_opaque(&s_single);
-      const double* tab = RTHX_TAB_PTR;
+      const double* tab = g_tab;
       const Emitter RTHX_LDS* em = lds_opaque(&s_emit);
       const Emitter& e = *(const Emitter*)em;
       const RayWords rw = ray_words<EK>(P, e, (uint32_t)g, r, have_pw, pw, FAITHFUL);
@@ -637,7 +629,7 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
       constexpr int EK = decltype(ek)::value;
       const SingleCoarse RTHX_LDS* scl = lds_opaque(&s_single);
       const SingleCoarse& sc = *(const SingleCoarse*)scl;
-      const double* tab = RTHX_TAB_PTR;
+      const double* tab = g_tab;
       const Emitter RTHX_LDS* em = lds_opaque(&s_emit);
       const Emitter& e = *(const Emitter*)em;
       const RayWords rw = ray_words<EK>(P, e, (uint32_t)g, r, true, pw, FAITHFUL);
@@ -687,7 +679,8 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
     const uint32_t n_rd = (uint32_t)__builtin_amdgcn_readfirstlane((int)((q1 - q0 + nt - 1u) / nt));
     // The loop is compiled twice: for an axis-aligned rectangle volume
     // emitter (the cells of a lattice: the kind tests of the emission fold
-    // away, EmitKind) and for any emitter.
+    // away, EmitKind) and for any emitter.  The four rays of a round are unrolled
+    // (one body, the word picked by k, was slower: profiles/round8/ab/ray_loop_items.log).
     auto rounds = [&](auto ek) {
     uint32_t q = q0 + (uint32_t)tid;
     uint32_t q_lo = q0;  // (scalar) the round's first group
@@ -708,22 +701,14 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
               out[k] = !(r >= rb && r < re);
             }
           }
-#if RTHX_ROUND_UNROLL
 #pragma unroll
-#else
-#pragma nounroll
-#endif
           for (uint32_t k = 0; k < 4u; ++k) {
             const uint32_t pw = k == 0u ? b[0] : k == 1u ? b[1] : k == 2u ? b[2] : b[3];
             const bool o = k == 0u ? out[0] : k == 1u ? out[1] : k == 2u ? out[2] : out[3];
             one_ray_lat(4u * q + k, pw, o, ek);
           }
         } else {
-#if RTHX_ROUND_UNROLL
 #pragma unroll
-#else
-#pragma nounroll
-#endif
         for (uint32_t k = 0; k < 4u; ++k) {
           uint32_t r = 4u * q + k;
           const uint32_t pw = k == 0u ? b[0] : k == 1u ? b[1] : k == 2u ? b[2] : b[3];
@@ -760,10 +745,6 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
     const uint64_t lt_mask = lane == 0 ? 0ull : (~0ull >> (64 - lane));
     double RTHX_LDS* q = (double RTHX_LDS*)(cl_base + D.ml.bytes) + (tid >> 6) * (64 * kRaySlotDoubles);
     __shared__ MBox s_box0;  // the emitter's coarse box: every ray of the row starts there
-#ifdef RTHX_SEGSTAT
-    __shared__ unsigned long long s_segs;  // (diagnostic build: segments walked by the row)
-    if (tid == 0) s_segs = 0ull;
-#endif
     if (tid == 0) ml_enter(mlat_lds_view(cl_base, D.ml), D.ml, s_emit.coarse, s_box0);
     __syncthreads();
     uint32_t q_head = 0, q_cnt = 0;  // wave-uniform ring of 64 slots
@@ -805,7 +786,7 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
         const uint32_t rr = base + lane;
         const bool valid = lane < want && rr < (uint32_t)r_end;
         if (valid) {
-          const double* tab = RTHX_TAB_PTR;
+          const double* tab = g_tab;
           const Emitter RTHX_LDS* em = lds_opaque(&s_emit);
           const Emitter& e = *(const Emitter*)em;
           double v[kRaySlotDoubles];
@@ -846,26 +827,14 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
       // the row has no rays left to hand out.
       const uint32_t stop = (!exhausted || q_cnt > 0) ? 64u - kRefillQ : 0u;
       if (live) {
-#ifdef RTHX_SEGSTAT
-        const int it0 = it;
-#endif
         if (layered && P.mixed)
           state = walk_layers<UNIFORM, true>(D, P, RTHX_ML_VIEW, RTHX_ML_G, box, px, py, ry, S, acc, it, u_end, stop);
         else if (layered)
           state = walk_layers<UNIFORM, false>(D, P, RTHX_ML_VIEW, RTHX_ML_G, box, px, py, ry, S, acc, it, u_end, stop);
         else
           state = walk_ml<UNIFORM>(D, P, RTHX_ML_VIEW, RTHX_ML_G, box, px, py, ry, S, acc, it, u_end, stop);
-#ifdef RTHX_SEGSTAT
-        atomicAdd(&s_segs, (unsigned long long)(it - it0));
-#endif
       }
     }
-#ifdef RTHX_SEGSTAT
-    __syncthreads();
-    if (tid == 0 && slot % 2048 == 0)
-      printf("SEGSTAT bin %d row %lld rays %lld segments %llu per_ray %.3f\n", P.bin, (long long)g,
-             (long long)(r_end - r_begin), s_segs, (double)s_segs / (double)(r_end - r_begin));
-#endif
   } else {
     // Several domains' rays cross many coarse polygons (the greenhouse's 67
     // layers), and their segment counts differ widely.  Ray regeneration: a
@@ -894,7 +863,7 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
           if (!live) {
             r = atomicAdd(&s_next, 1u);
             if (r < (uint32_t)r_end) {
-              const double* tab = RTHX_TAB_PTR;
+              const double* tab = g_tab;
               const Emitter RTHX_LDS* em = lds_opaque(&s_emit);
               const Emitter& e = *(const Emitter*)em;
               start_ray<UNIFORM, FAITHFUL>(P, e, (const double*)tab, (uint32_t)g, r, px, py, dx, dy, S);
@@ -1031,77 +1000,75 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
   // between launches.
   __shared__ uint32_t s_merge;  // bit 0: this part arrived last; bit 1: a packed pair overflowed 16 bits
   const int64_t wstride = (n_words + 3) & ~int64_t(3);  // slab words (whole uint4s)
-  const uint32_t* slabs = tail ? T.dense + (size_t)trow * parts * (size_t)wstride : nullptr;
+  const uint32_t* slabs = SPLIT ? T.dense + (size_t)trow * parts * (size_t)wstride : nullptr;
   if constexpr (SPLIT && !HASH) {
-    if (tail) {
-      const __amdgpu_buffer_rsrc_t srsrc =
-          __builtin_amdgcn_make_buffer_rsrc((void*)slabs, 0, (int)(parts * wstride * 4), kBufferRsrcWord3);
-      const u4 RTHX_LDS* h4 = (const u4 RTHX_LDS*)(uint32_t RTHX_LDS*)hist;
-      const uint32_t nq = (uint32_t)(wstride / 4);
-      for (uint32_t c = tid; c < nq; c += (uint32_t)nthr)
-        __builtin_amdgcn_raw_buffer_store_b128(h4[c], srsrc, (int)((tpart * wstride + 4 * c) * 4), 0, kSc1);
-      if (tid == 0)
-        __hip_atomic_store(&T.part_tallied[(size_t)trow * parts + tpart], s_tallied, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-      __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) {
-        // Memory-model ordering of the hand-off (not only the cache policy's):
-        // the barrier orders every wave's slab stores before this lane's
-        // agent-scope release, and the arrival is acquire as well, so the part
-        // that arrives last sees every other part's slab and tallied count;
-        // its barrier below hands that on to the lanes that read the slabs.
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        const uint32_t before =
-            __hip_atomic_fetch_add(&T.row_arrive[trow], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = before + 1u == parts;
-        if (last) {
-          __hip_atomic_store(&T.row_arrive[trow], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          uint32_t t = 0;
-          for (uint32_t p = 0; p < parts; ++p)
-            t += p == tpart ? s_tallied
-                            : __hip_atomic_load(&T.part_tallied[(size_t)trow * parts + p], __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT);
-          s_tallied = t;
-        }
-        s_merge = last ? 1u : 0u;
+    const __amdgpu_buffer_rsrc_t srsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void*)slabs, 0, (int)(parts * wstride * 4), kBufferRsrcWord3);
+    const u4 RTHX_LDS* h4 = (const u4 RTHX_LDS*)(uint32_t RTHX_LDS*)hist;
+    const uint32_t nq = (uint32_t)(wstride / 4);
+    for (uint32_t c = tid; c < nq; c += (uint32_t)nthr)
+      __builtin_amdgcn_raw_buffer_store_b128(h4[c], srsrc, (int)((tpart * wstride + 4 * c) * 4), 0, kSc1);
+    if (tid == 0)
+      __hip_atomic_store(&T.part_tallied[(size_t)trow * parts + tpart], s_tallied, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+      // Memory-model ordering of the hand-off (not only the cache policy's):
+      // the barrier orders every wave's slab stores before this lane's
+      // agent-scope release, and the arrival is acquire as well, so the part
+      // that arrives last sees every other part's slab and tallied count;
+      // its barrier below hands that on to the lanes that read the slabs.
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      const uint32_t before =
+          __hip_atomic_fetch_add(&T.row_arrive[trow], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+      const bool last = before + 1u == parts;
+      if (last) {
+        __hip_atomic_store(&T.row_arrive[trow], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint32_t t = 0;
+        for (uint32_t p = 0; p < parts; ++p)
+          t += p == tpart ? s_tallied
+                          : __hip_atomic_load(&T.part_tallied[(size_t)trow * parts + p], __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_AGENT);
+        s_tallied = t;
       }
-      __syncthreads();
-      if (!(s_merge & 1u)) return;
-      // The row's counts: the sum of its slabs (this part's own included).
-      // Packed 16-bit pairs cannot overflow when R < 65536; otherwise a pair
-      // that would leaves the histogram alone and the row is counted from
-      // the slabs.
-      u4 RTHX_LDS* w4 = (u4 RTHX_LDS*)(uint32_t RTHX_LDS*)hist;
-      bool ovf = false;
-      for (uint32_t c = tid; c < nq; c += (uint32_t)nthr) {
-        u4 lo = {0u, 0u, 0u, 0u}, hi = {0u, 0u, 0u, 0u};
-        for (uint32_t p0 = 0; p0 < parts; p0 += 4) {
-          u4 v[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            v[j] = p0 + j < parts
-                       ? __builtin_amdgcn_raw_buffer_load_b128(srsrc, (int)(((p0 + j) * wstride + 4 * c) * 4), 0, kSc1)
-                       : u4{0u, 0u, 0u, 0u};
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            lo += PACK16 ? (v[j] & 0xFFFFu) : v[j];
-            if (PACK16) hi += v[j] >> 16;
-          }
-        }
-        if (PACK16) {
-          const u4 o = lo | hi;
-          if ((o.x | o.y | o.z | o.w) > 0xFFFFu) ovf = true;
-          else w4[c] = lo | (hi << 16);
-        } else {
-          w4[c] = lo;
-        }
-      }
-      if (ovf) atomicOr(&s_merge, 2u);
-      __syncthreads();
+      s_merge = last ? 1u : 0u;
     }
+    __syncthreads();
+    if (!(s_merge & 1u)) return;
+    // The row's counts: the sum of its slabs (this part's own included).
+    // Packed 16-bit pairs cannot overflow when R < 65536; otherwise a pair
+    // that would leaves the histogram alone and the row is counted from
+    // the slabs.
+    u4 RTHX_LDS* w4 = (u4 RTHX_LDS*)(uint32_t RTHX_LDS*)hist;
+    bool ovf = false;
+    for (uint32_t c = tid; c < nq; c += (uint32_t)nthr) {
+      u4 lo = {0u, 0u, 0u, 0u}, hi = {0u, 0u, 0u, 0u};
+      for (uint32_t p0 = 0; p0 < parts; p0 += 4) {
+        u4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          v[j] = p0 + j < parts
+                     ? __builtin_amdgcn_raw_buffer_load_b128(srsrc, (int)(((p0 + j) * wstride + 4 * c) * 4), 0, kSc1)
+                     : u4{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          lo += PACK16 ? (v[j] & 0xFFFFu) : v[j];
+          if (PACK16) hi += v[j] >> 16;
+        }
+      }
+      if (PACK16) {
+        const u4 o = lo | hi;
+        if ((o.x | o.y | o.z | o.w) > 0xFFFFu) ovf = true;
+        else w4[c] = lo | (hi << 16);
+      } else {
+        w4[c] = lo;
+      }
+    }
+    if (ovf) atomicOr(&s_merge, 2u);
+    __syncthreads();
   }
-  const bool from_slabs = SPLIT && PACK16 && tail && __builtin_amdgcn_readfirstlane((int)(s_merge & 2u)) != 0;
+  const bool from_slabs = SPLIT && PACK16 && __builtin_amdgcn_readfirstlane((int)(s_merge & 2u)) != 0;
   auto count2 = [&](uint32_t w, uint32_t& lo, uint32_t& hi) {
     if (SPLIT && PACK16 && from_slabs) {  // (rare: R >= 65536 and one absorber took 65536 of them)
       lo = hi = 0u;
@@ -1466,26 +1433,23 @@ static hipError_t launch_trace_t(const LaunchCfg& L) {
   return hipGetLastError();
 }
 
-template <bool UNIFORM, int TALLY, bool FAITHFUL, bool AXIS>
-static hipError_t launch_trace_a(const LaunchCfg& L) {
+template <bool UNIFORM, int TALLY, bool FAITHFUL, bool AXIS, bool SPLIT>
+static hipError_t launch_trace_s(const LaunchCfg& L) {
   // SINGLE kernels with CL = 1: the lattice locate (LAT; axis-aligned only);
   // multi-polygon kernels: CL = 1 coarse mesh in LDS, 2 lattice (MLAT, axis only)
-  if (L.T.split > 1) {
-    if constexpr (AXIS) {
-      if (L.single && L.clds) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, true, false, true, AXIS, 1>(L);
-      if (!L.single && L.clds == 2) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, false, false, true, AXIS, 2>(L);
-    }
-    if (L.single) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, true, false, true, AXIS>(L);
-    if (L.clds) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, false, false, true, AXIS, 1>(L);
-    return launch_trace_t<UNIFORM, TALLY, FAITHFUL, false, false, true, AXIS>(L);
-  }
   if constexpr (AXIS) {
-    if (L.single && L.clds) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, true, false, false, AXIS, 1>(L);
-    if (!L.single && L.clds == 2) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, false, false, false, AXIS, 2>(L);
+    if (L.single && L.clds) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, true, false, SPLIT, AXIS, 1>(L);
+    if (!L.single && L.clds == 2) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, false, false, SPLIT, AXIS, 2>(L);
   }
-  if (L.single) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, true, false, false, AXIS>(L);
-  if (L.clds) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, false, false, false, AXIS, 1>(L);
-  return launch_trace_t<UNIFORM, TALLY, FAITHFUL, false, false, false, AXIS>(L);
+  if (L.single) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, true, false, SPLIT, AXIS>(L);
+  if (L.clds) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, false, false, SPLIT, AXIS, 1>(L);
+  return launch_trace_t<UNIFORM, TALLY, FAITHFUL, false, false, SPLIT, AXIS>(L);
+}
+
+template <bool UNIFORM, int TALLY, bool FAITHFUL, bool AXIS>
+static hipError_t launch_trace_a(const LaunchCfg& L) {
+  return L.T.split > 1 ? launch_trace_s<UNIFORM, TALLY, FAITHFUL, AXIS, true>(L)
+                       : launch_trace_s<UNIFORM, TALLY, FAITHFUL, AXIS, false>(L);
 }
 
 template <bool UNIFORM, int TALLY, bool FAITHFUL>

@@ -5,9 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace rthx {
+#include "rthx_device.h"  // RTHX_LDS
 
-#define RTHX_LDS __attribute__((address_space(3)))
+namespace rthx {
 
 // The same LDS address, hidden from the optimiser (one v_mov): loads through
 // it are not hoisted out of the ray loop.
