@@ -42,6 +42,9 @@ extern "C" {
 #endif
 
 #define RTHX_ABI_VERSION 5  /* 5: rthx_trace_exchange_rays, rthx_result_accumulate[_csr], rthx_result_sampling_error */
+/* Functions added since (rthx_csr_symmetrize, rthx_smooth_get_build) change no
+ * existing signature or struct: the version stays 5, and a caller that needs
+ * them looks the symbols up. */
 
 /* status codes */
 #define RTHX_OK 0
@@ -293,6 +296,26 @@ int rthx_csr_transpose(int32_t device, int64_t n_rows, int64_t n_cols, const int
                        const int32_t* cols, const double* vals, int64_t* t_row_ptr, int32_t* t_cols,
                        double* t_vals, double* device_ms);
 
+/* X = (Diagonal(w) A + (Diagonal(w) A)') / 2 of a square CSR matrix, on the
+ * device: the set-up of the sparse smoothing as a primitive.
+ * Host arrays in and out.  A: row_ptr[n + 1] (row_ptr[0] = 0, monotone),
+ * cols[nnz] in [0, n) strictly ascending within a row, finite vals[nnz];
+ * w[n] finite, or NULL for ones (else RTHX_EINVAL, checked on the host before
+ * any device call); n or nnz >= 2^31: RTHX_ERANGE.  X has the union of the
+ * patterns of A and A', columns strictly ascending, stored zeros kept:
+ * x_row_ptr[n + 1], x_cols and x_vals with room for x_cap entries (2 nnz
+ * always suffice) and *x_nnz, the entries of X.  With a_ij = RN(w_i v_ij) for
+ * a stored entry and +0.0 for an absent one, x_ij = RN(0.5 RN(a_ij + a_ji)):
+ * fixed to the bit, no atomics, the same bytes on every run.  If X has more
+ * than x_cap entries, x_row_ptr and *x_nnz (the size needed) are written,
+ * x_cols and x_vals are not touched, and the call returns RTHX_ERANGE.
+ * device_ms (may be NULL): hipEvent time of the transpose and symmetrise
+ * kernels together (with the read of X's size between them). */
+int rthx_csr_symmetrize(int32_t device, int64_t n, const int64_t* row_ptr, const int32_t* cols,
+                        const double* vals, const double* w /* [n] or NULL = 1 */,
+                        int64_t x_cap, int64_t* x_row_ptr /* [n+1] */, int32_t* x_cols /* [x_cap] */,
+                        double* x_vals /* [x_cap] */, int64_t* x_nnz, double* device_ms /* may be NULL */);
+
 /* Pin (page-lock) caller memory for direct device DMA, e.g. the cols/counts
  * arrays a caller reuses across traces; unregister before freeing it. */
 int rthx_host_register(void* ptr, size_t bytes);
@@ -433,6 +456,11 @@ int rthx_smooth_F(const int64_t* row_ptr, const int32_t* cols, const double* val
 int rthx_smooth_F_result(const rthx_result* counts, int64_t n, const double* w, int64_t n_w,
                          int32_t num_surfaces, const rthx_smooth_args* args, rthx_smooth_result** out);
 int rthx_smooth_get_info(const rthx_smooth_result* res, rthx_smooth_info* info);
+/* How a smoothing result's sparse X was formed: *x_on_device = 1 when built by the
+ * kernels of rthx_csr_symmetrize from device-resident counts, 0 otherwise (host
+ * CSR input, dense results); *x_build_ms = wall time of that build (0 for dense).
+ * Either pointer may be NULL. */
+int rthx_smooth_get_build(const rthx_smooth_result* res, int32_t* x_on_device, double* x_build_ms);
 /* Dense result: out[n*n], row-major. */
 int rthx_smooth_copy_dense(const rthx_smooth_result* res, double* out);
 /* Sparse result: row_ptr[n+1], cols[nnz], vals[nnz], columns ascending. */

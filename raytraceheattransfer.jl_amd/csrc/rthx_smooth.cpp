@@ -20,6 +20,7 @@
 #include "rthx_common.h"
 #include "rthx_domain.h"
 #include "rthx_smooth.h"
+#include "rthx_symmetrize.h"
 
 using rthx::DevBuf;
 using rthx::fail;
@@ -307,9 +308,6 @@ int smooth_core(const SmoothInput& in, const double* w_in, int64_t n_w, int32_t 
   const int64_t* rp = in.rp;
   const int32_t* ci = in.ci;
   const double* v = in.v;
-  std::vector<int64_t> h_rp;
-  std::vector<int32_t> h_ci;
-  std::vector<double> h_v;
   const bool verbose = args->verbose != 0;
   const int64_t N = n_w;  // length(w)
   double chi = 0.0, nz_over_N;
@@ -466,49 +464,43 @@ int smooth_core(const SmoothInput& in, const double* w_in, int64_t n_w, int32_t 
     res->nnz = m * m;
   } else {
     const double t2 = now_ms();
+    int64_t xnnz = 0;
     if (in.counts) {
-      // the sparse X pattern is built on the host: bring the block's
-      // normalised F_raw over once (rows < m, columns < m)
-      const rthx_result* cr = in.counts;
-      std::vector<int64_t> ro(m + 1);
-      std::vector<uint32_t> cc, cn;
-      std::vector<double> rs(m);
-      DTRY(hipMemcpy(ro.data(), cr->row_off.p, (m + 1) * 8, hipMemcpyDeviceToHost), "hipMemcpy row_off");
-      cc.resize(std::max<int64_t>(ro[m], 1));
-      cn.resize(std::max<int64_t>(ro[m], 1));
-      if (ro[m]) {
-        DTRY(hipMemcpy(cc.data(), cr->cols.p, ro[m] * 4, hipMemcpyDeviceToHost), "hipMemcpy cols");
-        DTRY(hipMemcpy(cn.data(), cr->cnt.p, ro[m] * 4, hipMemcpyDeviceToHost), "hipMemcpy counts");
+      // X from the block's counts where they lie: F' by the
+      // device transpose, then the row merge of F and F' with the weights
+      // already uploaded; only the size of X crosses the host link
+      rthx::tp::Block B;
+      rthx::sym::Work W;
+      RTRY(rthx::tp::result_block(in.counts, m, s, B));
+      RTRY(rthx::sym::reserve(B.S, W));
+      DTRY(res->rp.reserve((m + 1) * 8), "hipMalloc");
+      DTRY(rthx::sym::enqueue_lengths(B.S, W, res->rp.as<int64_t>(), s), "symmetrise lengths");
+      DTRY(hipMemcpyAsync(&xnnz, res->rp.as<int64_t>() + m, 8, hipMemcpyDeviceToHost, s), "hipMemcpy X nnz");
+      DTRY(hipStreamSynchronize(s), "symmetrise lengths");
+      DTRY(res->ci.reserve(std::max<int64_t>(xnnz, 1) * 4), "hipMalloc");
+      DTRY(res->F.reserve(std::max<int64_t>(xnnz, 1) * 8), "hipMalloc");
+      DTRY(rthx::sym::enqueue_write(B.S, W, c.dv(c.w), res->rp.as<int64_t>(), res->ci.as<int32_t>(),
+                                    res->F.as<double>(), s),
+           "symmetrise write");
+      DTRY(hipStreamSynchronize(s), "symmetrise");
+      res->x_on_device = true;  // (F', the scratch and the marks go out of scope here, before AP)
+    } else {
+      std::vector<int64_t> xrp;
+      std::vector<int32_t> xci;
+      std::vector<double> xv;
+      build_x_sparse(rp, ci, v, w, m, xrp, xci, xv);
+      xnnz = xrp[m];
+      DTRY(res->rp.reserve((m + 1) * 8), "hipMalloc");
+      DTRY(res->ci.reserve(std::max<int64_t>(xnnz, 1) * 4), "hipMalloc");
+      DTRY(res->F.reserve(std::max<int64_t>(xnnz, 1) * 8), "hipMalloc");
+      DTRY(hipMemcpyAsync(res->rp.p, xrp.data(), (m + 1) * 8, hipMemcpyHostToDevice, s), "hipMemcpy");
+      if (xnnz) {
+        DTRY(hipMemcpyAsync(res->ci.p, xci.data(), xnnz * 4, hipMemcpyHostToDevice, s), "hipMemcpy");
+        DTRY(hipMemcpyAsync(res->F.p, xv.data(), xnnz * 8, hipMemcpyHostToDevice, s), "hipMemcpy");
       }
-      DTRY(hipMemcpy(rs.data(), in.tallied, m * 8, hipMemcpyDeviceToHost), "hipMemcpy tallied");
-      h_rp.assign(m + 1, 0);
-      h_ci.reserve(nnz);
-      h_v.reserve(nnz);
-      for (int64_t i = 0; i < m; ++i) {
-        for (int64_t k = ro[i]; k < ro[i + 1]; ++k)
-          if ((int64_t)cc[k] < m) {
-            h_ci.push_back((int32_t)cc[k]);
-            h_v.push_back((double)cn[k] / rs[i]);
-          }
-        h_rp[i + 1] = (int64_t)h_ci.size();
-      }
-      rp = h_rp.data();
-      ci = h_ci.data();
-      v = h_v.data();
+      DTRY(hipStreamSynchronize(s), "X upload");
     }
-    std::vector<int64_t> xrp;
-    std::vector<int32_t> xci;
-    std::vector<double> xv;
-    build_x_sparse(rp, ci, v, w, m, xrp, xci, xv);
-    const int64_t xnnz = xrp[m];
-    DTRY(res->rp.reserve((m + 1) * 8), "hipMalloc");
-    DTRY(res->ci.reserve(std::max<int64_t>(xnnz, 1) * 4), "hipMalloc");
-    DTRY(res->F.reserve(std::max<int64_t>(xnnz, 1) * 8), "hipMalloc");
-    DTRY(hipMemcpyAsync(res->rp.p, xrp.data(), (m + 1) * 8, hipMemcpyHostToDevice, s), "hipMemcpy");
-    if (xnnz) {
-      DTRY(hipMemcpyAsync(res->ci.p, xci.data(), xnnz * 4, hipMemcpyHostToDevice, s), "hipMemcpy");
-      DTRY(hipMemcpyAsync(res->F.p, xv.data(), xnnz * 8, hipMemcpyHostToDevice, s), "hipMemcpy");
-    }
+    res->x_build_ms = now_ms() - t2;
     if (verbose) std::printf("Alternating projection (AP): parallel, sparse\n");
     RTRY(ap_sparse(c, res, args->max_iters, nz_over_N, st));
     DTRY(hipStreamSynchronize(s), "AP");
@@ -653,6 +645,13 @@ RTHX_EXPORT int rthx_smooth_F_result(const rthx_result* cr, int64_t n, const dou
 RTHX_EXPORT int rthx_smooth_get_info(const rthx_smooth_result* res, rthx_smooth_info* info) {
   if (!res || !info) return fail(RTHX_EINVAL, "null argument");
   *info = res->info;
+  return RTHX_OK;
+}
+
+RTHX_EXPORT int rthx_smooth_get_build(const rthx_smooth_result* res, int32_t* x_on_device, double* x_build_ms) {
+  if (!res) return fail(RTHX_EINVAL, "null argument");
+  if (x_on_device) *x_on_device = res->x_on_device ? 1 : 0;
+  if (x_build_ms) *x_build_ms = res->x_build_ms;
   return RTHX_OK;
 }
 

@@ -23,6 +23,8 @@ struct rthx_smooth_result {
   int64_t nnz = 0;
   rthx::DevBuf trp, tci, tv;  // F' as CSR (sparse results)
   bool have_t = false;
+  bool x_on_device = false;  // sparse X built by rthx_symmetrize_kernels.hip (rthx_smooth_get_build)
+  double x_build_ms = 0.0;   // wall time of the sparse X build, host or device
   rthx_smooth_info info{};
   ~rthx_smooth_result() {
     if (device >= 0) (void)hipSetDevice(device);

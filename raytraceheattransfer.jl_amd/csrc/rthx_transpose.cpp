@@ -18,35 +18,44 @@ using rthx::fail;
 namespace rthx {
 namespace tp {
 
-int transpose_result_block(const rthx_result* res, int64_t n, hipStream_t st, Transposed& out) {
+int result_block(const rthx_result* res, int64_t n, hipStream_t st, Block& B) {
   if (res->info.nnz >= (int64_t(1) << 31)) return fail(RTHX_ERANGE, "nnz must be below 2^31 for the device transpose");
-  DevBuf tallied, src, len, off, scratch;
-  HIP_TRY(tallied.reserve((size_t)n * 8), "hipMalloc tallied");
-  HIP_TRY(src.reserve((size_t)n * 8), "hipMalloc row starts");
+  DevBuf len;
+  HIP_TRY(B.tallied.reserve((size_t)n * 8), "hipMalloc tallied");
+  HIP_TRY(B.src.reserve((size_t)n * 8), "hipMalloc row starts");
   HIP_TRY(len.reserve((size_t)n * 8), "hipMalloc row lengths");
-  HIP_TRY(off.reserve((size_t)(n + 1) * 8), "hipMalloc row offsets");
+  HIP_TRY(B.off.reserve((size_t)(n + 1) * 8), "hipMalloc row offsets");
   HIP_TRY(block_rows(res->row_off.as<int64_t>(), res->cols.as<uint32_t>(), res->cnt.as<uint32_t>(), n, n, res->N,
-                     tallied.as<double>(), src.as<int64_t>(), len.as<int64_t>(), off.as<int64_t>(), st),
+                     B.tallied.as<double>(), B.src.as<int64_t>(), len.as<int64_t>(), B.off.as<int64_t>(), st),
           "block rows launch");
   int64_t nnz = 0;
-  HIP_TRY(hipMemcpyAsync(&nnz, off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st), "hipMemcpy block nnz");
+  HIP_TRY(hipMemcpyAsync(&nnz, B.off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st), "hipMemcpy block nnz");
   HIP_TRY(hipStreamSynchronize(st), "block rows");
+  Source& S = B.S;
+  S.n_rows = n;
+  S.n_cols = n;
+  S.nnz = nnz;
+  S.off = B.off.as<int64_t>();
+  S.src = B.src.as<int64_t>();
+  S.whole = 0;
+  S.cols = res->cols.as<uint32_t>();
+  S.counts = res->cnt.as<uint32_t>();
+  S.tallied = B.tallied.as<double>();
+  return RTHX_OK;
+}
+
+int transpose_result_block(const rthx_result* res, int64_t n, hipStream_t st, Transposed& out) {
+  Block B;
+  if (int rc = result_block(res, n, st, B)) return rc;
+  const Source& S = B.S;
+  const int64_t nnz = S.nnz;
+  DevBuf scratch;
   const Plan P = plan_transpose(n, nnz, 4);
   HIP_TRY(scratch.reserve((size_t)P.scratch_bytes), "hipMalloc transpose scratch");
   HIP_TRY(out.rp.reserve((size_t)(n + 1) * 8), "hipMalloc");
   HIP_TRY(out.ci.reserve((size_t)std::max<int64_t>(nnz, 1) * 4), "hipMalloc");
   HIP_TRY(out.v.reserve((size_t)std::max<int64_t>(nnz, 1) * 8), "hipMalloc");
   out.nnz = nnz;
-  Source S;
-  S.n_rows = n;
-  S.n_cols = n;
-  S.nnz = nnz;
-  S.off = off.as<int64_t>();
-  S.src = src.as<int64_t>();
-  S.whole = 0;
-  S.cols = res->cols.as<uint32_t>();
-  S.counts = res->cnt.as<uint32_t>();
-  S.tallied = tallied.as<double>();
   Dest D;
   D.t_off = out.rp.as<int64_t>();
   D.rows32 = out.ci.as<int32_t>();

@@ -60,8 +60,17 @@ struct Transposed {
   int64_t nnz = 0;
 };
 
-// The n x n leading block of a trace result's F_raw (count / tallied),
-// transposed on the result's device.  The result is ready, single-device and
+// The n x n leading block of a trace result's F_raw (count / tallied) as a
+// Source over the counts where they lie, with the row arrays it points to.
+// The result is ready, single-device and holds every row < n (checked by the
+// caller).
+struct Block {
+  DevBuf tallied, src, off;
+  Source S;
+};
+int result_block(const rthx_result* res, int64_t n, hipStream_t st, Block& B);
+
+// That block transposed on the result's device.  The result is ready, single-device and
 // holds every row < n (checked by the caller).
 int transpose_result_block(const rthx_result* res, int64_t n, hipStream_t st, Transposed& out);
 // A sparse smoothing result's F', formed on first use and kept in the handle.

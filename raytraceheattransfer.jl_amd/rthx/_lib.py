@@ -109,6 +109,11 @@ def load(path: Optional[str] = None) -> C.CDLL:
         lib.rthx_csr_transpose.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int64),
                                            C.POINTER(C.c_int32), dp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), dp,
                                            dp]
+    if hasattr(lib, "rthx_csr_symmetrize"):  # (older A/B variant libraries lack both)
+        lib.rthx_csr_symmetrize.argtypes = [C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), dp, dp,
+                                            C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), dp,
+                                            C.POINTER(C.c_int64), dp]
+        lib.rthx_smooth_get_build.argtypes = [C.c_void_p, C.POINTER(C.c_int32), dp]
     pb = C.POINTER(abi.SpectralBand)
     lib.rthx_solve_spectral.argtypes = [pb, C.c_int32, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, dp,
                                         C.POINTER(abi.SpectralArgs), dp, dp, dp, dp, C.POINTER(abi.SpectralInfo)]

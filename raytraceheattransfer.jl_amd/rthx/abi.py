@@ -305,6 +305,7 @@ EXPORTED_SYMBOLS = (
     "rthx_result_copy_F",
     "rthx_result_copy_F_csc",
     "rthx_csr_transpose",
+    "rthx_csr_symmetrize",
     "rthx_result_get_device_csr",
     "rthx_result_copy_csr_device",
     "rthx_merge_row_shards",
@@ -316,6 +317,7 @@ EXPORTED_SYMBOLS = (
     "rthx_smooth_F",
     "rthx_smooth_F_result",
     "rthx_smooth_get_info",
+    "rthx_smooth_get_build",
     "rthx_smooth_copy_dense",
     "rthx_smooth_copy_csr",
     "rthx_smooth_destroy",

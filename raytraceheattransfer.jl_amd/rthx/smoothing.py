@@ -86,6 +86,14 @@ def _fetch(lib, h, inf):
     return sp.csr_matrix((ov[:inf.nnz], oci[:inf.nnz], orp), shape=(m, m))
 
 
+def _build_facts(lib, h) -> dict:
+    """rthx_smooth_get_build: whether a sparse X was built on the device, and
+    the wall time of its build."""
+    on_device, ms = C.c_int32(0), C.c_double(0.0)
+    check(lib.rthx_smooth_get_build(h, C.byref(on_device), C.byref(ms)))
+    return {"x_on_device": int(on_device.value), "x_build_ms": ms.value}
+
+
 def smooth_F_device(result, n: int, w, num_surfaces: int, max_iters: int = 1000,
                     smooth_surfaces_only: bool = False, k_dykstra: Optional[int] = None, verbose: bool = True,
                     renorm: bool = True, device: int = 0, info: Optional[dict] = None) -> SmoothHandle:
@@ -106,6 +114,7 @@ def smooth_F_device(result, n: int, w, num_surfaces: int, max_iters: int = 1000,
         raise
     if info is not None:
         info.update(inf.as_dict())
+        info.update(_build_facts(lib, h))
     return SmoothHandle(lib, h, device, bool(inf.dense), inf)
 
 
@@ -137,6 +146,7 @@ def smooth_F(F_raw, w, num_surfaces: int, max_iters: int = 1000, smooth_surfaces
         out = _fetch(lib, h, inf)
         if info is not None:
             info.update(inf.as_dict())
+            info.update(_build_facts(lib, h))
     except Exception:
         lib.rthx_smooth_destroy(h)
         raise
@@ -168,6 +178,40 @@ def csr_transpose(A, device: int = 0, info: Optional[dict] = None) -> sp.csr_mat
     if info is not None:
         info["device_ms"] = ms.value
     return sp.csr_matrix((tv[:nnz], tci[:nnz], trp), shape=(n_cols, n_rows))
+
+
+def csr_symmetrize(A, w=None, device: int = 0, info: Optional[dict] = None) -> sp.csr_matrix:
+    """X = (Diagonal(w) A + (Diagonal(w) A)') / 2 of a square matrix as CSR,
+    formed on the device (rthx_csr_symmetrize): the union of the patterns of A
+    and A', every row in ascending column order, stored zeros kept, and
+    x_ij = 0.5 * (w_i a_ij + w_j a_ji) rounded after each operation (``w``
+    None: ones).  Rows are sorted and duplicates summed first, as smooth_F
+    does.  ``info`` (optional dict) receives ``device_ms``, the time of the
+    transpose and symmetrise kernels."""
+    lib = load()
+    A = sp.csr_matrix(A, copy=True)
+    A.sum_duplicates()
+    n = A.shape[0]
+    if A.shape[1] != n:
+        raise ValueError("csr_symmetrize needs a square matrix")
+    rp = np.ascontiguousarray(A.indptr, dtype=np.int64)
+    ci = np.ascontiguousarray(A.indices, dtype=np.int32)
+    vv = np.ascontiguousarray(A.data, dtype=np.float64)
+    ww = None if w is None else np.ascontiguousarray(w, dtype=np.float64)
+    if ww is not None and len(ww) != n:
+        raise ValueError("w must have one entry per row")
+    cap = 2 * int(rp[-1])
+    xrp = np.empty(n + 1, dtype=np.int64)
+    xci = np.empty(max(cap, 1), dtype=np.int32)
+    xv = np.empty(max(cap, 1))
+    xnnz, ms = C.c_int64(0), C.c_double(0.0)
+    check(lib.rthx_csr_symmetrize(device, n, abi.ptr(rp, C.c_int64), abi.ptr(ci, C.c_int32), abi.ptr(vv, C.c_double),
+                                  abi.ptr(ww, C.c_double), cap, abi.ptr(xrp, C.c_int64), abi.ptr(xci, C.c_int32),
+                                  abi.ptr(xv, C.c_double), C.byref(xnnz), C.byref(ms)))
+    if info is not None:
+        info["device_ms"] = ms.value
+    k = xnnz.value
+    return sp.csr_matrix((xv[:k].copy(), xci[:k].copy(), xrp), shape=(n, n))
 
 
 def result_device(res) -> int:
