@@ -89,6 +89,15 @@ hipError_t lib_stream(int device, hipStream_t* out, int which) {
 
 hipError_t device_stream(int device, hipStream_t* out) { return lib_stream(device, out, 0); }
 hipError_t copy_stream(int device, hipStream_t* out) { return lib_stream(device, out, 1); }
+
+int open_device(int device, hipStream_t* stream) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(RTHX_EDEVICE, "no HIP device visible");
+  if (device < 0 || device >= ndev) return fail(RTHX_EINVAL, "device ordinal out of range");
+  HIP_TRY(hipSetDevice(device), "hipSetDevice");
+  if (stream) HIP_TRY(device_stream(device, stream), "hipStreamCreate");
+  return RTHX_OK;
+}
 }  // namespace rthx
 
 namespace rthx {
@@ -274,10 +283,7 @@ RTHX_EXPORT int rthx_domain_create(const rthx_domain_desc* desc, int32_t device,
     if (rc) return rc;
   }
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(RTHX_EDEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(RTHX_EINVAL, "device ordinal out of range");
-  HIP_TRY(hipSetDevice(device), "hipSetDevice");
+  RTHX_TRY(rthx::open_device(device, nullptr));  // (the stream: below, once the handle exists)
 
   rthx_domain* d = new (std::nothrow) rthx_domain();
   if (!d) return fail(RTHX_ENOMEM, "host allocation failed");

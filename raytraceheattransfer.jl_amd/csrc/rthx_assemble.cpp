@@ -39,8 +39,8 @@ RTHX_EXPORT int rthx_merge_row_shards(int32_t device, int32_t n_shards, int64_t 
 // F_raw in CSC (include/rthx.h rthx_result_copy_F_csc).  One-device results:
 // the transpose kernels of rthx_transpose_kernels.hip on the counts where
 // they lie (counts payload, int64 rows), then three D2H copies.  Several
-// devices' parts: F_raw as CSR on the host (rthx_result_copy_F) and a
-// counting-sort transpose there.
+// devices' parts: F_raw as CSR on the host (rthx_result_copy_F) and the host
+// transpose of rthx_csr_host.h.
 #include <algorithm>
 #include <cmath>
 #include <utility>
@@ -57,17 +57,9 @@ int csc_on_host(rthx_result* res, int64_t base, int64_t* colptr, int64_t* rowval
   std::vector<int32_t> cols((size_t)std::max<int64_t>(nnz, 1));
   std::vector<double> vals((size_t)std::max<int64_t>(nnz, 1));
   if (int rc = rthx_result_copy_F(res, rp.data(), cols.data(), vals.data())) return rc;
-  std::vector<int64_t> next((size_t)N + 1, 0);
-  for (int64_t i = 0; i < nnz; ++i) ++next[(size_t)cols[(size_t)i] + 1];
-  for (int64_t c = 0; c < N; ++c) next[(size_t)c + 1] += next[(size_t)c];
-  if (colptr)
-    for (int64_t c = 0; c <= N; ++c) colptr[c] = next[(size_t)c] + base;
-  for (int64_t g = 0; g < N; ++g)  // rows in ascending order: each column's rows come out ascending
-    for (int64_t i = rp[(size_t)g]; i < rp[(size_t)g + 1]; ++i) {
-      const int64_t pos = next[(size_t)cols[(size_t)i]]++;
-      if (rowval) rowval[pos] = g + base;
-      if (nzval) nzval[pos] = vals[(size_t)i];
-    }
+  std::vector<int64_t> own_colptr(colptr ? 0 : (size_t)N + 1);
+  rthx::csr::transpose(rp.data(), cols.data(), vals.data(), N, N, base, colptr ? colptr : own_colptr.data(), rowval,
+                       nzval);
   return RTHX_OK;
 }
 
@@ -99,20 +91,11 @@ RTHX_EXPORT int rthx_result_copy_F_csc(const rthx_result* cres, int32_t index_ba
   HIP_TRY(res->csc_rowval.reserve(m * 8), "hipMalloc rowval");
   HIP_TRY(res->csc_nz.reserve(m * 8), "hipMalloc nzval");
   // every traced row whole (n_keep = N): the rows' tallied rays, and offsets from 0
-  HIP_TRY(tp::block_rows(res->row_off.as<int64_t>(), res->cols.as<uint32_t>(), res->cnt.as<uint32_t>(), n_rows, N, N,
-                         res->csc_rowsum.as<double>(), res->csc_src.as<int64_t>(), res->csc_len.as<int64_t>(),
-                         res->csc_off.as<int64_t>(), st),
-          "CSC rows launch");
   tp::Source S;
-  S.n_rows = n_rows;
-  S.n_cols = N;
+  HIP_TRY(tp::counts_source(res, n_rows, N, res->csc_rowsum.as<double>(), res->csc_src.as<int64_t>(),
+                            res->csc_len.as<int64_t>(), res->csc_off.as<int64_t>(), st, S),
+          "CSC rows launch");
   S.nnz = nnz;
-  S.off = res->csc_off.as<int64_t>();
-  S.src = res->csc_src.as<int64_t>();
-  S.whole = 1;
-  S.cols = res->cols.as<uint32_t>();
-  S.counts = res->cnt.as<uint32_t>();
-  S.tallied = res->csc_rowsum.as<double>();
   tp::Dest D;
   D.t_off = res->csc_colptr.as<int64_t>();
   D.rows64 = res->csc_rowval.as<int64_t>();
@@ -134,11 +117,6 @@ RTHX_EXPORT int rthx_result_copy_F_csc(const rthx_result* cres, int32_t index_ba
 // (rthx_result_sampling_error).  Kernels: rthx_assemble_kernels.hip.
 // ---------------------------------------------------------------------------
 namespace {
-
-void swap_buf(rthx::DevBuf& a, rthx::DevBuf& b) {
-  std::swap(a.p, b.p);
-  std::swap(a.cap, b.cap);
-}
 
 // dst += the block (b_off, b_cols, b_cnt) of dst->n_rows rows, nnz_b entries
 // and rays_b rays per row, on dst's device (dst is ready, single-device).
@@ -195,9 +173,9 @@ int accumulate_block(rthx_result* dst, const int64_t* b_off, const uint32_t* b_c
   HIP_TRY(hipEventElapsedTime(&ms, dst->acc_ev[0], dst->acc_ev[1]), "hipEventElapsedTime");
   dst->acc_ms = ms;
   // the sum takes the result's place; the old arrays serve the next accumulate
-  swap_buf(dst->row_off, dst->acc_off);
-  swap_buf(dst->cols, dst->acc_cols);
-  swap_buf(dst->cnt, dst->acc_cnt);
+  dst->row_off.swap(dst->acc_off);
+  dst->cols.swap(dst->acc_cols);
+  dst->cnt.swap(dst->acc_cnt);
   dst->host_row_off = false;
   dst->R += rays_b;
   dst->info.rays_per_emitter = dst->R;

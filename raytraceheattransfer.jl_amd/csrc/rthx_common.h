@@ -1,14 +1,18 @@
-// rthx_common.h -- host-side helpers shared by the C-ABI translation units
-// (rthx_api.cpp, rthx_smooth.cpp): exported-symbol macro, thread-local error
-// message, HIP error mapping, grow-only device / pinned host buffers.
+// rthx_common.h -- host-side helpers shared by the C-ABI translation units:
+// exported-symbol macro, thread-local error message, HIP error mapping and the
+// return-on-error macros, the check of a caller's host CSR with its message
+// recorded, grow-only device / pinned host buffers, a pair of
+// timing events, and the opening of a device with the library's stream on it.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <chrono>
 #include <string>
+#include <utility>
 
 #include "../../include/rthx.h"
+#include "rthx_csr_host.h"
 
 #define RTHX_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -30,6 +34,23 @@ inline int hip_fail(hipError_t e, const char* what) {
     hipError_t _e = (expr);                              \
     if (_e != hipSuccess) return rthx::hip_fail(_e, what); \
   } while (0)
+
+// Returns the rc of a call that has already recorded its message (fail).
+#define RTHX_TRY(expr)              \
+  do {                              \
+    int _rc = (expr);               \
+    if (_rc != RTHX_OK) return _rc; \
+  } while (0)
+
+// The check of a caller's host CSR (rthx::csr::check, rthx_csr_host.h) with
+// its refusal recorded by fail.
+template <class Visit = csr::NoVisit>
+int check_host_csr(const int64_t* row_ptr, const int32_t* cols, const double* vals, int64_t n_rows, int64_t n_cols,
+                   bool below_2g, bool ascending, Visit* visitor = nullptr) {
+  std::string msg;
+  const int rc = csr::check(row_ptr, cols, vals, n_rows, n_cols, below_2g, ascending, msg, visitor);
+  return rc ? fail(rc, msg) : RTHX_OK;
+}
 
 // Device buffer with grow-only capacity.
 // Tuning and test knobs from the environment (RTHX_NO_AXIS, RTHX_FORCE_HASH,
@@ -65,6 +86,10 @@ struct DevBuf {
     if (p) (void)hipFree(p);
     p = nullptr;
     cap = 0;
+  }
+  void swap(DevBuf& o) {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
   }
   template <class T>
   T* as() const { return static_cast<T*>(p); }
@@ -127,5 +152,29 @@ hipError_t device_stream(int device, hipStream_t* out);
 // finished result (rthx_result_copy_csr_device), so that the next trace on
 // the device stream does not queue behind them.
 hipError_t copy_stream(int device, hipStream_t* out);
+// Makes `device` the calling thread's current device: RTHX_EDEVICE without a
+// visible device, RTHX_EINVAL for an ordinal out of range.  stream (optional)
+// receives device_stream(device).
+int open_device(int device, hipStream_t* stream);
+
+// Two events around a stretch of a stream and the device time between them.
+struct EventPair {
+  hipEvent_t e[2] = {nullptr, nullptr};
+  EventPair() = default;
+  EventPair(const EventPair&) = delete;
+  EventPair& operator=(const EventPair&) = delete;
+  ~EventPair() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  hipError_t create() {
+    const hipError_t err = hipEventCreate(&e[0]);
+    return err != hipSuccess ? err : hipEventCreate(&e[1]);
+  }
+  hipError_t start(hipStream_t s) { return hipEventRecord(e[0], s); }
+  hipError_t stop(hipStream_t s) { return hipEventRecord(e[1], s); }
+  // (the stop event has completed: the caller synchronised the stream or the event)
+  hipError_t elapsed(float* ms) { return hipEventElapsedTime(ms, e[0], e[1]); }
+};
 
 }  // namespace rthx

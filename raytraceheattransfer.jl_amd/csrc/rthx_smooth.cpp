@@ -6,6 +6,8 @@
 // dense/sparse switch, Dykstra-round choice, the defect schedule of AP with
 // its contraction estimate and floor acceptance -- follows the reference
 // line by line; the numerical passes differ from it only in summation order.
+// The caller's CSR is checked, and the host route's sparse X built, by
+// rthx_csr_host.h; host matrices go up as a tp::DeviceCsr (rthx_transpose.h).
 // host-only translation unit: device pointers are plain pointers here
 #define RTHX_HOST_ONLY_TU 1
 #include <hip/hip_runtime.h>
@@ -14,6 +16,7 @@
 #include <cmath>
 #include <cstdio>
 #include <limits>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -29,12 +32,6 @@ using rthx::now_ms;
 namespace {
 
 constexpr double kEps = std::numeric_limits<double>::epsilon();
-
-#define TRY(expr)                \
-  do {                           \
-    int _rc = (expr);            \
-    if (_rc != RTHX_OK) return _rc; \
-  } while (0)
 
 // Work vectors of one smoothing call (all length n).
 struct Ctx {
@@ -72,25 +69,25 @@ int solve_R(Ctx& c, const double* bvec, double* xout, int* iters) {
   HIP_TRY(vmul(c.dv(c.d_dinv), r, n, z, s), "vmul");
   HIP_TRY(hipMemcpyAsync(p, z, n * sizeof(double), hipMemcpyDeviceToDevice, s), "hipMemcpy");
   double rz, bb;
-  TRY(c.dot(r, z, n, &rz));
-  TRY(c.dot(bvec, bvec, n, &bb));
+  RTHX_TRY(c.dot(r, z, n, &rz));
+  RTHX_TRY(c.dot(bvec, bvec, n, &bb));
   const double bn = std::sqrt(bb);
   const int maxiter = 200;
   for (int it = 1; it <= maxiter; ++it) {
     HIP_TRY(rmul(c.dv(c.w2), c.dv(c.d_rowsum), p, n, Ap, s), "rmul");
     double pAp;
-    TRY(c.dot(p, Ap, n, &pAp));
+    RTHX_TRY(c.dot(p, Ap, n, &pAp));
     const double alpha = rz / pAp;
     HIP_TRY(pcg_xr(xout, r, p, Ap, alpha, n, s), "pcg_xr");
     double rr;
-    TRY(c.dot(r, r, n, &rr));
+    RTHX_TRY(c.dot(r, r, n, &rr));
     if (std::sqrt(rr) <= 1e-14 * bn) {
       *iters = it;
       return RTHX_OK;
     }
     HIP_TRY(vmul(c.dv(c.d_dinv), r, n, z, s), "vmul");
     double rz_new;
-    TRY(c.dot(r, z, n, &rz_new));
+    RTHX_TRY(c.dot(r, z, n, &rz_new));
     const double beta = rz_new / rz;
     HIP_TRY(pcg_p(p, z, beta, n, s), "pcg_p");
     rz = rz_new;
@@ -104,7 +101,7 @@ int ensure_dual(Ctx& c) {
   if (c.dual_ready) return RTHX_OK;
   const int64_t n = c.n;
   DevBuf* vs[] = {&c.d_rowsum, &c.d_dinv, &c.b, &c.x, &c.pr, &c.z, &c.p, &c.Ap, &c.rs};
-  for (DevBuf* v : vs) TRY(c.alloc(*v, n, "hipMalloc dual vectors"));
+  for (DevBuf* v : vs) RTHX_TRY(c.alloc(*v, n, "hipMalloc dual vectors"));
   HIP_TRY(rthx::sm::dual_setup(c.dv(c.w2), n, c.dv(c.d_rowsum), c.dv(c.d_dinv), c.s), "dual_setup");
   c.dual_ready = true;
   return RTHX_OK;
@@ -125,17 +122,17 @@ int ap_loop(Ctx& c, int max_iters, double nz_over_N, Step step, Delta delta_of, 
   const double sw = 4 * guard;
   const int max_stride = 52;
   double delta;
-  TRY(delta_of(&delta));
+  RTHX_TRY(delta_of(&delta));
   double delta_init = delta, delta_best = delta;
   if (c.verbose) std::printf("  after first reciprocity projection: delta_R = %.6g\n", delta);
   int k = 0, k_next = 0, cnt = 0, flat = 0, k_prev = 0;
   double delta_prev = delta, rho_est = 0.5;
   bool floor_accepted = false;
   while (k < max_iters && delta > target) {
-    TRY(step());  // scale! then hunger!
+    RTHX_TRY(step());  // scale! then hunger!
     k += 1;
     if (k >= k_next) {
-      TRY(delta_of(&delta));
+      RTHX_TRY(delta_of(&delta));
       cnt += 1;
       if (cnt >= 3) {
         rho_est = std::min(std::max(std::pow(delta / delta_prev, 1.0 / std::max(k - k_prev, 1)), 0.5), 0.9999);
@@ -186,75 +183,26 @@ int ap_dense(Ctx& c, double* F, double* X, int max_iters, double nz_over_N, APSt
   const int64_t n = c.n, ld = ap_dense_ld(n);
   hipStream_t s = c.s;
   HIP_TRY(build_x(F, c.dv(c.w), n, ld, X, s), "build_x");
-  TRY(c.alloc(c.rowpart, ap_sym_col_tiles(n) * n, "hipMalloc AP partial sums"));
-  TRY(c.alloc(c.colpart, ap_sym_row_tiles(n) * n, "hipMalloc AP partial sums"));
+  RTHX_TRY(c.alloc(c.rowpart, ap_sym_col_tiles(n) * n, "hipMalloc AP partial sums"));
+  RTHX_TRY(c.alloc(c.colpart, ap_sym_row_tiles(n) * n, "hipMalloc AP partial sums"));
   HIP_TRY(ap_sym(X, ld, c.dv(c.u), c.dv(c.w), n, false, c.dv(c.rowpart), c.dv(c.colpart), c.dv(c.r), c.dv(c.u), s),
           "hunger");
   auto delta_of = [&](double* d) {
     HIP_TRY(delta_rows(X, ld, c.dv(c.u), c.dv(c.w2), n, c.dv(c.part), s), "delta_rows");
     double ss;
-    TRY(c.dot(c.dv(c.part), nullptr, n, &ss));
+    RTHX_TRY(c.dot(c.dv(c.part), nullptr, n, &ss));
     *d = std::sqrt(ss);
     return RTHX_OK;
   };
   auto step = [&]() {
     HIP_TRY(ap_sym(X, ld, c.dv(c.u), c.dv(c.w), n, true, c.dv(c.rowpart), c.dv(c.colpart), c.dv(c.r), c.dv(c.u2), s),
             "ap_step");
-    std::swap(c.u.p, c.u2.p);
-    std::swap(c.u.cap, c.u2.cap);
+    c.u.swap(c.u2);
     return RTHX_OK;
   };
-  TRY(ap_loop(c, max_iters, nz_over_N, step, delta_of, st));
+  RTHX_TRY(ap_loop(c, max_iters, nz_over_N, step, delta_of, st));
   HIP_TRY(recover_sym(X, ld, c.dv(c.r), n, F, s), "recover");
   return RTHX_OK;
-}
-
-// Sparse X = (Diagonal(w) F + (Diagonal(w) F)') / 2 (:474-477) on the host:
-// union pattern, columns ascending, entries present once contribute a / 2.
-void build_x_sparse(const int64_t* rp, const int32_t* ci, const double* v, const std::vector<double>& w, int64_t n,
-                    std::vector<int64_t>& xrp, std::vector<int32_t>& xci, std::vector<double>& xv) {
-  const int64_t nnz = rp[n];
-  // transpose of A = Diagonal(w) F
-  std::vector<int64_t> trp(n + 1, 0);
-  for (int64_t k = 0; k < nnz; ++k) trp[ci[k] + 1]++;
-  for (int64_t i = 0; i < n; ++i) trp[i + 1] += trp[i];
-  std::vector<int32_t> tci(nnz);
-  std::vector<double> tv(nnz);
-  {
-    std::vector<int64_t> pos(trp.begin(), trp.end() - 1);
-    for (int64_t i = 0; i < n; ++i)
-      for (int64_t k = rp[i]; k < rp[i + 1]; ++k) {
-        const int64_t q = pos[ci[k]]++;
-        tci[q] = (int32_t)i;  // rows visited in ascending order: columns of the transpose ascend
-        tv[q] = w[i] * v[k];
-      }
-  }
-  xrp.assign(n + 1, 0);
-  xci.clear();
-  xv.clear();
-  xci.reserve(2 * nnz);
-  xv.reserve(2 * nnz);
-  for (int64_t i = 0; i < n; ++i) {
-    int64_t a = rp[i], ae = rp[i + 1], b = trp[i], be = trp[i + 1];
-    while (a < ae || b < be) {
-      const int32_t ca = a < ae ? ci[a] : INT32_MAX, cb = b < be ? tci[b] : INT32_MAX;
-      if (ca == cb) {
-        xci.push_back(ca);
-        xv.push_back(0.5 * (w[i] * v[a] + tv[b]));
-        ++a;
-        ++b;
-      } else if (ca < cb) {
-        xci.push_back(ca);
-        xv.push_back(0.5 * (w[i] * v[a] + 0.0));
-        ++a;
-      } else {
-        xci.push_back(cb);
-        xv.push_back(0.5 * (0.0 + tv[b]));
-        ++b;
-      }
-    }
-    xrp[i + 1] = (int64_t)xci.size();
-  }
 }
 
 // Sparse AP on the device: X in res->rp / res->ci / res->F.
@@ -269,17 +217,16 @@ int ap_sparse(Ctx& c, rthx_smooth_result* res, int max_iters, double nz_over_N, 
   auto delta_of = [&](double* d) {
     HIP_TRY(sp_delta_rows(rp, ci, v, c.dv(c.u), c.dv(c.w2), n, c.dv(c.part), s), "sp_delta_rows");
     double ss;
-    TRY(c.dot(c.dv(c.part), nullptr, n, &ss));
+    RTHX_TRY(c.dot(c.dv(c.part), nullptr, n, &ss));
     *d = std::sqrt(ss);
     return RTHX_OK;
   };
   auto step = [&]() {
     HIP_TRY(sp_step(rp, ci, v, c.dv(c.u), c.dv(c.w), n, true, c.dv(c.r), c.dv(c.u2), s), "sp_step");
-    std::swap(c.u.p, c.u2.p);
-    std::swap(c.u.cap, c.u2.cap);
+    c.u.swap(c.u2);
     return RTHX_OK;
   };
-  TRY(ap_loop(c, max_iters, nz_over_N, step, delta_of, st));
+  RTHX_TRY(ap_loop(c, max_iters, nz_over_N, step, delta_of, st));
   HIP_TRY(sp_recover(rp, v, c.dv(c.r), n, s), "sp_recover");
   return RTHX_OK;
 }
@@ -351,14 +298,10 @@ int smooth_core(const SmoothInput& in, const double* w_in, int64_t n_w, int32_t 
       return fail(RTHX_EINVAL, "Smoothing convergence check failed: max surface w >= half of total w");
   }
 
-  rthx_smooth_result* res = new (std::nothrow) rthx_smooth_result();
+  std::unique_ptr<rthx_smooth_result> res(new (std::nothrow) rthx_smooth_result());  // (released into *out at the end)
   if (!res) return fail(RTHX_ENOMEM, "host allocation failed");
-  auto bail = [&](int code) {
-    delete res;
-    return code;
-  };
   res->device = args->device;
-  if (rthx::device_stream(args->device, &res->stream) != hipSuccess) return bail(fail(RTHX_EDEVICE, "hipStreamCreate"));
+  HIP_TRY(rthx::device_stream(args->device, &res->stream), "hipStreamCreate");
   Ctx c;
   c.s = res->stream;
   c.n = m;
@@ -370,21 +313,10 @@ int smooth_core(const SmoothInput& in, const double* w_in, int64_t n_w, int32_t 
     inv_w[i] = 1.0 / w[i];
   }
   DevBuf* vecs[] = {&c.w, &c.w2, &c.inv_w, &c.r, &c.u, &c.u2, &c.part, &c.scal};
-  for (DevBuf* b : vecs)
-    if (int rc = c.alloc(*b, m, "hipMalloc vectors")) return bail(rc);
-#define DTRY(expr, what)                                      \
-  do {                                                        \
-    hipError_t _e = (expr);                                   \
-    if (_e != hipSuccess) return bail(rthx::hip_fail(_e, what)); \
-  } while (0)
-#define RTRY(expr)                 \
-  do {                             \
-    int _rc = (expr);              \
-    if (_rc != RTHX_OK) return bail(_rc); \
-  } while (0)
-  DTRY(hipMemcpyAsync(c.w.p, w.data(), m * 8, hipMemcpyHostToDevice, s), "hipMemcpy w");
-  DTRY(hipMemcpyAsync(c.w2.p, w2.data(), m * 8, hipMemcpyHostToDevice, s), "hipMemcpy w2");
-  DTRY(hipMemcpyAsync(c.inv_w.p, inv_w.data(), m * 8, hipMemcpyHostToDevice, s), "hipMemcpy inv_w");
+  for (DevBuf* b : vecs) RTHX_TRY(c.alloc(*b, m, "hipMalloc vectors"));
+  HIP_TRY(hipMemcpyAsync(c.w.p, w.data(), m * 8, hipMemcpyHostToDevice, s), "hipMemcpy w");
+  HIP_TRY(hipMemcpyAsync(c.w2.p, w2.data(), m * 8, hipMemcpyHostToDevice, s), "hipMemcpy w2");
+  HIP_TRY(hipMemcpyAsync(c.inv_w.p, inv_w.data(), m * 8, hipMemcpyHostToDevice, s), "hipMemcpy inv_w");
 
   APState st;
   double t_op = 0, t_ap = 0;
@@ -392,74 +324,66 @@ int smooth_core(const SmoothInput& in, const double* w_in, int64_t n_w, int32_t 
   if (dense) {
     const size_t bytes = (size_t)m * (size_t)m * 8;
     DevBuf A, Xb, P;
-    DTRY(A.reserve(bytes), "hipMalloc dense F");
-    DTRY(Xb.reserve((size_t)m * (size_t)ap_dense_ld(m) * 8), "hipMalloc dense X");  // also Xbar (n x n)
+    HIP_TRY(A.reserve(bytes), "hipMalloc dense F");
+    HIP_TRY(Xb.reserve((size_t)m * (size_t)ap_dense_ld(m) * 8), "hipMalloc dense X");  // also Xbar (n x n)
     // dense F_raw (truncated to m x m): the CSR rows < m, columns < m
     if (in.counts) {
-      DTRY(hipMemsetAsync(A.p, 0, bytes, s), "hipMemset");
-      DTRY(rthx::sm::scatter_counts(in.counts->row_off.as<int64_t>(), in.counts->cols.as<uint32_t>(),
-                                    in.counts->cnt.as<uint32_t>(), m, in.tallied, A.as<double>(), s),
-           "scatter_counts");
-      DTRY(hipStreamSynchronize(s), "scatter");
+      HIP_TRY(hipMemsetAsync(A.p, 0, bytes, s), "hipMemset");
+      HIP_TRY(rthx::sm::scatter_counts(in.counts->row_off.as<int64_t>(), in.counts->cols.as<uint32_t>(),
+                                       in.counts->cnt.as<uint32_t>(), m, in.tallied, A.as<double>(), s),
+              "scatter_counts");
+      HIP_TRY(hipStreamSynchronize(s), "scatter");
     } else {
-      DevBuf drp, dci, dv;
-      const int64_t mnnz = rp[m];
-      DTRY(drp.reserve((m + 1) * 8), "hipMalloc");
-      DTRY(dci.reserve(std::max<int64_t>(mnnz, 1) * 4), "hipMalloc");
-      DTRY(dv.reserve(std::max<int64_t>(mnnz, 1) * 8), "hipMalloc");
-      DTRY(hipMemcpyAsync(drp.p, rp, (m + 1) * 8, hipMemcpyHostToDevice, s), "hipMemcpy");
-      if (mnnz) {
-        DTRY(hipMemcpyAsync(dci.p, ci, mnnz * 4, hipMemcpyHostToDevice, s), "hipMemcpy");
-        DTRY(hipMemcpyAsync(dv.p, v, mnnz * 8, hipMemcpyHostToDevice, s), "hipMemcpy");
-      }
-      DTRY(hipMemsetAsync(A.p, 0, bytes, s), "hipMemset");
-      DTRY(rthx::sm::scatter(drp.as<int64_t>(), dci.as<int32_t>(), dv.as<double>(), m, A.as<double>(), s), "scatter");
-      DTRY(hipStreamSynchronize(s), "scatter");
+      rthx::tp::DeviceCsr D;
+      RTHX_TRY(D.upload(rp, ci, v, m, rp[m], s));
+      HIP_TRY(hipMemsetAsync(A.p, 0, bytes, s), "hipMemset");
+      HIP_TRY(rthx::sm::scatter(D.rp.as<int64_t>(), D.ci.as<int32_t>(), D.v.as<double>(), m, A.as<double>(), s),
+              "scatter");
+      HIP_TRY(hipStreamSynchronize(s), "scatter");
     }
     double* F = A.as<double>();
     double* X = Xb.as<double>();
     if (k_dykstra > 0) {
       // DkAP (:299-318)
       const double t1 = now_ms();
-      RTRY(ensure_dual(c));
+      RTHX_TRY(ensure_dual(c));
       if (k_dykstra > 1) {
-        DTRY(P.reserve(bytes), "hipMalloc dense P");
-        DTRY(hipMemsetAsync(P.p, 0, bytes, s), "hipMemset P");
+        HIP_TRY(P.reserve(bytes), "hipMalloc dense P");
+        HIP_TRY(hipMemsetAsync(P.p, 0, bytes, s), "hipMemset P");
       }
       double delta = std::numeric_limits<double>::infinity();
       for (int k = 1; k <= k_dykstra; ++k) {
         rounds = k;
-        DTRY(rthx::sm::xbar(F, c.dv(c.inv_w), c.dv(c.w2), m, X, s), "xbar");
-        DTRY(rthx::sm::rowsum(X, m, c.dv(c.rs), s), "rowsum");
-        DTRY(rthx::sm::make_b(c.dv(c.rs), c.dv(c.w), false, m, c.dv(c.b), s), "make_b");
-        RTRY(solve_R(c, c.dv(c.b), c.dv(c.x), &pcg_iters));
-        DTRY(rthx::sm::op_dykstra(X, c.dv(c.x), c.dv(c.w2), c.dv(c.inv_w), m, k_dykstra > 1 ? P.as<double>() : nullptr,
-                                  k < k_dykstra, F, s),
-             "op_dykstra");
+        HIP_TRY(rthx::sm::xbar(F, c.dv(c.inv_w), c.dv(c.w2), m, X, s), "xbar");
+        HIP_TRY(rthx::sm::rowsum(X, m, c.dv(c.rs), s), "rowsum");
+        HIP_TRY(rthx::sm::make_b(c.dv(c.rs), c.dv(c.w), false, m, c.dv(c.b), s), "make_b");
+        RTHX_TRY(solve_R(c, c.dv(c.b), c.dv(c.x), &pcg_iters));
+        HIP_TRY(rthx::sm::op_dykstra(X, c.dv(c.x), c.dv(c.w2), c.dv(c.inv_w), m,
+                                     k_dykstra > 1 ? P.as<double>() : nullptr, k < k_dykstra, F, s),
+                "op_dykstra");
         if (k % 5 == 0 || k == k_dykstra) {
           // delta_perp (:132-138, mode :DYK)
-          DTRY(rthx::sm::rowsum(F, m, c.dv(c.rs), s), "rowsum");
-          DTRY(rthx::sm::make_b(c.dv(c.rs), c.dv(c.w), true, m, c.dv(c.b), s), "make_b");
+          HIP_TRY(rthx::sm::rowsum(F, m, c.dv(c.rs), s), "rowsum");
+          HIP_TRY(rthx::sm::make_b(c.dv(c.rs), c.dv(c.w), true, m, c.dv(c.b), s), "make_b");
           int it2 = 0;
-          RTRY(solve_R(c, c.dv(c.b), c.dv(c.x), &it2));
+          RTHX_TRY(solve_R(c, c.dv(c.b), c.dv(c.x), &it2));
           double bl;
-          RTRY(c.dot(c.dv(c.b), c.dv(c.x), m, &bl));
+          RTHX_TRY(c.dot(c.dv(c.b), c.dv(c.x), m, &bl));
           delta = std::sqrt(bl);
           if (verbose) std::printf("Dykstra round %d (%d PCG iterations): delta_perp = %.6g\n", k, pcg_iters, delta);
         }
         if (delta < 8 * kEps) break;
       }
-      DTRY(rthx::sm::renorm(F, m, s), "renorm");
-      DTRY(hipStreamSynchronize(s), "Dykstra");
+      HIP_TRY(rthx::sm::renorm(F, m, s), "renorm");
+      HIP_TRY(hipStreamSynchronize(s), "Dykstra");
       t_op = now_ms() - t1;
     }
     const double t2 = now_ms();
     if (verbose) std::printf("Alternating projection (AP): parallel, dense\n");
-    RTRY(ap_dense(c, F, X, args->max_iters, nz_over_N, st));
-    DTRY(hipStreamSynchronize(s), "AP");
+    RTHX_TRY(ap_dense(c, F, X, args->max_iters, nz_over_N, st));
+    HIP_TRY(hipStreamSynchronize(s), "AP");
     t_ap = now_ms() - t2;
-    std::swap(res->F.p, A.p);  // ap_dense leaves F_smooth in the F buffer
-    std::swap(res->F.cap, A.cap);
+    res->F.swap(A);  // ap_dense leaves F_smooth in the F buffer
     res->dense = true;
     res->nnz = m * m;
   } else {
@@ -471,45 +395,38 @@ int smooth_core(const SmoothInput& in, const double* w_in, int64_t n_w, int32_t 
       // already uploaded; only the size of X crosses the host link
       rthx::tp::Block B;
       rthx::sym::Work W;
-      RTRY(rthx::tp::result_block(in.counts, m, s, B));
-      RTRY(rthx::sym::reserve(B.S, W));
-      DTRY(res->rp.reserve((m + 1) * 8), "hipMalloc");
-      DTRY(rthx::sym::enqueue_lengths(B.S, W, res->rp.as<int64_t>(), s), "symmetrise lengths");
-      DTRY(hipMemcpyAsync(&xnnz, res->rp.as<int64_t>() + m, 8, hipMemcpyDeviceToHost, s), "hipMemcpy X nnz");
-      DTRY(hipStreamSynchronize(s), "symmetrise lengths");
-      DTRY(res->ci.reserve(std::max<int64_t>(xnnz, 1) * 4), "hipMalloc");
-      DTRY(res->F.reserve(std::max<int64_t>(xnnz, 1) * 8), "hipMalloc");
-      DTRY(rthx::sym::enqueue_write(B.S, W, c.dv(c.w), res->rp.as<int64_t>(), res->ci.as<int32_t>(),
-                                    res->F.as<double>(), s),
-           "symmetrise write");
-      DTRY(hipStreamSynchronize(s), "symmetrise");
+      RTHX_TRY(rthx::tp::result_block(in.counts, m, s, B));
+      RTHX_TRY(rthx::sym::reserve(B.S, W));
+      HIP_TRY(res->rp.reserve((m + 1) * 8), "hipMalloc");
+      HIP_TRY(rthx::sym::enqueue_lengths(B.S, W, res->rp.as<int64_t>(), s), "symmetrise lengths");
+      HIP_TRY(hipMemcpyAsync(&xnnz, res->rp.as<int64_t>() + m, 8, hipMemcpyDeviceToHost, s), "hipMemcpy X nnz");
+      HIP_TRY(hipStreamSynchronize(s), "symmetrise lengths");
+      HIP_TRY(res->ci.reserve(std::max<int64_t>(xnnz, 1) * 4), "hipMalloc");
+      HIP_TRY(res->F.reserve(std::max<int64_t>(xnnz, 1) * 8), "hipMalloc");
+      HIP_TRY(rthx::sym::enqueue_write(B.S, W, c.dv(c.w), res->rp.as<int64_t>(), res->ci.as<int32_t>(),
+                                       res->F.as<double>(), s),
+              "symmetrise write");
+      HIP_TRY(hipStreamSynchronize(s), "symmetrise");
       res->x_on_device = true;  // (F', the scratch and the marks go out of scope here, before AP)
     } else {
-      std::vector<int64_t> xrp;
-      std::vector<int32_t> xci;
-      std::vector<double> xv;
-      build_x_sparse(rp, ci, v, w, m, xrp, xci, xv);
-      xnnz = xrp[m];
-      DTRY(res->rp.reserve((m + 1) * 8), "hipMalloc");
-      DTRY(res->ci.reserve(std::max<int64_t>(xnnz, 1) * 4), "hipMalloc");
-      DTRY(res->F.reserve(std::max<int64_t>(xnnz, 1) * 8), "hipMalloc");
-      DTRY(hipMemcpyAsync(res->rp.p, xrp.data(), (m + 1) * 8, hipMemcpyHostToDevice, s), "hipMemcpy");
-      if (xnnz) {
-        DTRY(hipMemcpyAsync(res->ci.p, xci.data(), xnnz * 4, hipMemcpyHostToDevice, s), "hipMemcpy");
-        DTRY(hipMemcpyAsync(res->F.p, xv.data(), xnnz * 8, hipMemcpyHostToDevice, s), "hipMemcpy");
-      }
-      DTRY(hipStreamSynchronize(s), "X upload");
+      rthx::csr::Host X;  // (rthx_csr_host.h: the layout and the bits of the device build)
+      rthx::csr::symmetric_part(rp, ci, v, w.data(), m, X);
+      xnnz = X.nnz();
+      rthx::tp::DeviceCsr D;
+      RTHX_TRY(D.upload(X.rp.data(), X.ci.data(), X.v.data(), m, xnnz, s));
+      HIP_TRY(hipStreamSynchronize(s), "X upload");
+      res->rp.swap(D.rp);
+      res->ci.swap(D.ci);
+      res->F.swap(D.v);
     }
     res->x_build_ms = now_ms() - t2;
     if (verbose) std::printf("Alternating projection (AP): parallel, sparse\n");
-    RTRY(ap_sparse(c, res, args->max_iters, nz_over_N, st));
-    DTRY(hipStreamSynchronize(s), "AP");
+    RTHX_TRY(ap_sparse(c, res.get(), args->max_iters, nz_over_N, st));
+    HIP_TRY(hipStreamSynchronize(s), "AP");
     t_ap = now_ms() - t2;
     res->dense = false;
     res->nnz = xnnz;
   }
-#undef DTRY
-#undef RTRY
   res->n = m;
   rthx_smooth_info& I = res->info;
   I.n = m;
@@ -526,7 +443,7 @@ int smooth_core(const SmoothInput& in, const double* w_in, int64_t n_w, int32_t 
   I.ms_op = t_op;
   I.ms_ap = t_ap;
   I.ms_total = now_ms() - t0;
-  *out = res;
+  *out = res.release();
   return RTHX_OK;
 }
 
@@ -540,32 +457,34 @@ RTHX_EXPORT int rthx_smooth_F(const int64_t* row_ptr, const int32_t* cols, const
   *out = nullptr;
   if (!row_ptr || !w_in || !args || n < 1 || n_w < n) return fail(RTHX_EINVAL, "bad smoothing arguments");
   if (n >= (1ll << 31)) return fail(RTHX_ERANGE, "matrix too large");
+  // (these two of the shared check's refusals stay ahead of the weights' and of the device's, where callers know them)
   if (row_ptr[0] != 0) return fail(RTHX_EINVAL, "row_ptr[0] != 0");
   const int64_t nnz = row_ptr[n];
   if (nnz > 0 && (!cols || !vals)) return fail(RTHX_EINVAL, "null CSR arrays");
   for (int64_t i = 0; i < n_w; ++i)
     if (!(w_in[i] > 0) || !std::isfinite(w_in[i])) return fail(RTHX_EINVAL, "weights must be positive and finite");
   if (num_surfaces < 0 || num_surfaces > n_w) return fail(RTHX_EINVAL, "num_surfaces out of range");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(RTHX_EDEVICE, "no HIP device visible");
-  if (args->device < 0 || args->device >= ndev) return fail(RTHX_EINVAL, "device ordinal out of range");
-  HIP_TRY(hipSetDevice(args->device), "hipSetDevice");
+  RTHX_TRY(rthx::open_device(args->device, nullptr));
 
-  // One pass over F_raw: validation, row order, and the surface-gas coupling
-  // sum of cross_coupling_chi (:212-241).  Rows must be sorted by column for
-  // the sparse build; unsorted input is sorted into a copy.
-  double chi_acc = 0.0;
-  bool sorted = true;
-  for (int64_t i = 0; i < n; ++i) {
-    if (row_ptr[i + 1] < row_ptr[i] || row_ptr[i + 1] > nnz) return fail(RTHX_EINVAL, "row_ptr not monotone");
-    const bool si = i < num_surfaces;
-    for (int64_t k = row_ptr[i]; k < row_ptr[i + 1]; ++k) {
-      const int32_t c = cols[k];
-      if (c < 0 || c >= n || !std::isfinite(vals[k])) return fail(RTHX_EINVAL, "bad CSR entry");
-      if (k > row_ptr[i] && !(cols[k - 1] < c)) sorted = false;
-      if (si != (c < num_surfaces)) chi_acc += vals[k];
+  // One pass over F_raw (rthx_csr_host.h): validation, row order, and the
+  // surface-gas coupling sum of cross_coupling_chi (:212-241).  Rows must be
+  // sorted by column for the sparse build; unsorted input is sorted into a copy.
+  struct Pass {
+    const int32_t* cols;
+    const double* vals;
+    int64_t num_surfaces;
+    int64_t row = -1;
+    double chi_acc = 0.0;
+    bool sorted = true;
+    void operator()(int64_t i, int64_t k) {
+      if (i == row && !(cols[k - 1] < cols[k])) sorted = false;
+      if ((i < num_surfaces) != (cols[k] < num_surfaces)) chi_acc += vals[k];
+      row = i;
     }
-  }
+  } pass{cols, vals, num_surfaces};
+  RTHX_TRY(rthx::check_host_csr(row_ptr, cols, vals, n, n, false, false, &pass));
+  const double chi_acc = pass.chi_acc;
+  const bool sorted = pass.sorted;
   std::vector<int32_t> ci_sorted;
   std::vector<double> v_sorted;
   const int64_t* rp = row_ptr;

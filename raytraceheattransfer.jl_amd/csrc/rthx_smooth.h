@@ -7,10 +7,11 @@
 #include <stdint.h>
 
 #include "rthx_common.h"
+#include "rthx_transpose.h"
 
 // The smoothing result handle (opaque in include/rthx.h).  The solvers
 // (rthx_solve.cpp, rthx_spectral.cpp) read a dense result in place; of a
-// sparse one they read F' (trp / tci / tv), formed on the device on first use
+// sparse one they read F' (t), formed on the device on first use
 // (rthx_transpose.h smooth_transposed) and kept here.  rp / ci / F stay as
 // they are for rthx_smooth_copy_csr.
 struct rthx_smooth_result {
@@ -21,7 +22,7 @@ struct rthx_smooth_result {
   rthx::DevBuf F;           // dense result (n*n, row-major) or sparse values
   rthx::DevBuf rp, ci;      // sparse pattern
   int64_t nnz = 0;
-  rthx::DevBuf trp, tci, tv;  // F' as CSR (sparse results)
+  rthx::tp::DeviceCsr t;    // F' as CSR (sparse results)
   bool have_t = false;
   bool x_on_device = false;  // sparse X built by rthx_symmetrize_kernels.hip (rthx_smooth_get_build)
   double x_build_ms = 0.0;   // wall time of the sparse X build, host or device
@@ -30,10 +31,7 @@ struct rthx_smooth_result {
     if (device >= 0) (void)hipSetDevice(device);
     F.release();
     rp.release();
-    ci.release();  // (stream: the device's shared stream)
-    trp.release();
-    tci.release();
-    tv.release();
+    ci.release();  // (stream: the device's shared stream; t frees itself next, on this device)
   }
 };
 

@@ -8,7 +8,9 @@
 // Gram-Schmidt applied twice (two batched kernels per step, one host sync)
 // instead of Krylov.jl's modified Gram-Schmidt; both keep the basis
 // orthogonal to working precision.  The Hessenberg least-squares problem
-// (Givens rotations, back substitution) is solved on the host.
+// (Givens rotations, back substitution) is solved on the host.  A caller's
+// sparse F is checked and transposed on the host by rthx_csr_host.h, before
+// the device is opened, and uploaded as a tp::DeviceCsr (rthx_transpose.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,12 +30,6 @@ using rthx::fail;
 using rthx::now_ms;
 
 namespace {
-
-#define STRY(expr)                  \
-  do {                              \
-    int _rc = (expr);               \
-    if (_rc != RTHX_OK) return _rc; \
-  } while (0)
 
 struct Solver : rthx::gs::Krylov {
   rthx::gs::Op op;
@@ -65,7 +61,7 @@ int Krylov::d2h(double* dst, const double* src, size_t count) {
 int Krylov::norm(const double* v, double* out) {
   HIP_TRY(multidot(v, v, 1, n, small.as<double>(), s), "multidot");
   double t;
-  STRY(d2h(&t, small.as<double>(), 1));
+  RTHX_TRY(d2h(&t, small.as<double>(), 1));
   *out = std::sqrt(t);
   return RTHX_OK;
 }
@@ -82,13 +78,13 @@ int gmres(Krylov& S, const Apply& A, const rthx_solve_args& a, bool warm, rthx_s
   double* h = S.h.as<double>();
   double* sm = S.small.as<double>();  // [2(m+1) + 1]: h1, h2, |w|^2
   double hnorm;
-  STRY(S.norm(h, &hnorm));
+  RTHX_TRY(S.norm(h, &hnorm));
   const double tol = a.atol + a.rtol * hnorm;
   double beta = hnorm;
   if (warm) {  // r = h - M x0
     HIP_TRY(A(x, w), "apply");
     HIP_TRY(sub(h, w, n, r, s), "sub");
-    STRY(S.norm(r, &beta));
+    RTHX_TRY(S.norm(r, &beta));
   } else {
     HIP_TRY(hipMemsetAsync(x, 0, n * 8, s), "hipMemset");
     HIP_TRY(hipMemcpyAsync(r, h, n * 8, hipMemcpyDeviceToDevice, s), "hipMemcpy");
@@ -111,7 +107,7 @@ int gmres(Krylov& S, const Apply& A, const rthx_solve_args& a, bool warm, rthx_s
       HIP_TRY(multidot(V, w, k + 1, n, sm + (m + 1), s), "multidot");
       HIP_TRY(combine(V, sm + (m + 1), k + 1, -1.0, n, w, s), "combine");
       HIP_TRY(multidot(w, w, 1, n, sm + 2 * (m + 1), s), "multidot");
-      STRY(S.d2h(hh.data(), sm, 2 * (m + 1) + 1));
+      RTHX_TRY(S.d2h(hh.data(), sm, 2 * (m + 1) + 1));
       for (int i = 0; i <= k; ++i) Hat(i, k) = hh[i] + hh[(m + 1) + i];
       const double hn = std::sqrt(hh[2 * (m + 1)]);
       Hat(k + 1, k) = hn;
@@ -141,40 +137,13 @@ int gmres(Krylov& S, const Apply& A, const rthx_solve_args& a, bool warm, rthx_s
     HIP_TRY(combine(V, sm, k, 1.0, n, x, s), "combine");
     HIP_TRY(A(x, w), "apply");  // true residual h - M x
     HIP_TRY(sub(h, w, n, r, s), "sub");
-    STRY(S.norm(r, &beta));
+    RTHX_TRY(S.norm(r, &beta));
   }
   info.iterations = (int32_t)iters;
   info.cycles = cycles;
   info.converged = beta <= tol ? 1 : 0;
   info.residual = beta;
   info.tolerance = tol;
-  return RTHX_OK;
-}
-
-// F' as CSR: counting sort by column (rows visited in order: columns of F' ascend)
-int csr_transpose(const int64_t* row_ptr, const int32_t* cols, const double* vals, int64_t n,
-                  std::vector<int64_t>& rp, std::vector<int32_t>& ci, std::vector<double>& v) {
-  if (!row_ptr || row_ptr[0] != 0) return fail(RTHX_EINVAL, "bad row_ptr");
-  const int64_t nnz = row_ptr[n];
-  if (nnz > 0 && (!cols || !vals)) return fail(RTHX_EINVAL, "null CSR arrays");
-  rp.assign(n + 1, 0);
-  for (int64_t i = 0; i < n; ++i) {
-    if (row_ptr[i + 1] < row_ptr[i]) return fail(RTHX_EINVAL, "row_ptr not monotone");
-    for (int64_t k = row_ptr[i]; k < row_ptr[i + 1]; ++k) {
-      if (cols[k] < 0 || cols[k] >= n || !std::isfinite(vals[k])) return fail(RTHX_EINVAL, "bad CSR entry");
-      rp[cols[k] + 1]++;
-    }
-  }
-  for (int64_t i = 0; i < n; ++i) rp[i + 1] += rp[i];
-  ci.assign(std::max<int64_t>(nnz, 1), 0);
-  v.assign(std::max<int64_t>(nnz, 1), 0.0);
-  std::vector<int64_t> pos(rp.begin(), rp.end() - 1);
-  for (int64_t i = 0; i < n; ++i)
-    for (int64_t k = row_ptr[i]; k < row_ptr[i + 1]; ++k) {
-      const int64_t q = pos[cols[k]]++;
-      ci[q] = (int32_t)i;
-      v[q] = vals[k];
-    }
   return RTHX_OK;
 }
 
@@ -188,17 +157,17 @@ int run(Solver& S, const double* coeff, const double* h, const rthx_solve_args* 
         rthx_solve_info* info, double t0) {
   const int64_t n = S.n;
   HIP_TRY(S.c.reserve(n * 8), "hipMalloc");
-  STRY(S.reserve(args->memory));
+  RTHX_TRY(S.reserve(args->memory));
   HIP_TRY(hipMemcpyAsync(S.c.p, coeff, n * 8, hipMemcpyHostToDevice, S.s), "hipMemcpy");
   HIP_TRY(hipMemcpyAsync(S.h.p, h, n * 8, hipMemcpyHostToDevice, S.s), "hipMemcpy");
   rthx_solve_info I{};
   I.n = n;
   const double* c = S.c.as<double>();
   const rthx::gs::Apply M = [&S, c](const double* x, double* out) { return rthx::gs::apply(S.op, x, c, out, S.s); };
-  STRY(rthx::gs::gmres(S, M, *args, false, I));
+  RTHX_TRY(rthx::gs::gmres(S, M, *args, false, I));
   HIP_TRY(rthx::gs::apply(S.op, S.x.as<double>(), nullptr, S.w.as<double>(), S.s), "apply");  // g = F' j
-  STRY(S.d2h(j_out, S.x.as<double>(), n));
-  STRY(S.d2h(g_out, S.w.as<double>(), n));
+  RTHX_TRY(S.d2h(j_out, S.x.as<double>(), n));
+  RTHX_TRY(S.d2h(g_out, S.w.as<double>(), n));
   I.ms_total = now_ms() - t0;
   if (info) *info = I;
   return RTHX_OK;
@@ -220,16 +189,18 @@ RTHX_EXPORT int rthx_solve_grey(const int64_t* row_ptr, const int32_t* cols, con
                                 const rthx_solve_args* args, double* j_out, double* g_out,
                                 rthx_solve_info* info) {
   const double t0 = now_ms();
-  STRY(check_args(n, coeff, h, args, j_out, g_out));
+  RTHX_TRY(check_args(n, coeff, h, args, j_out, g_out));
   if (n >= (1ll << 31)) return fail(RTHX_ERANGE, "system too large");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(RTHX_EDEVICE, "no HIP device visible");
-  if (args->device < 0 || args->device >= ndev) return fail(RTHX_EINVAL, "device ordinal out of range");
-  HIP_TRY(hipSetDevice(args->device), "hipSetDevice");
+  rthx::csr::Host Ft;  // F' of a sparse F
+  if (!dense) {
+    RTHX_TRY(rthx::check_host_csr(row_ptr, cols, vals, n, n, false, false));
+    rthx::csr::transposed(row_ptr, cols, vals, n, n, Ft);
+  }
   Solver S;
   S.n = n;
-  HIP_TRY(rthx::device_stream(args->device, &S.s), "hipStreamCreate");
-  DevBuf Fd, trp, tci, tv;
+  RTHX_TRY(rthx::open_device(args->device, &S.s));
+  DevBuf Fd;
+  rthx::tp::DeviceCsr T;
   S.op.n = n;
   if (dense) {
     for (int64_t k = 0; k < n * n; ++k)
@@ -241,21 +212,12 @@ RTHX_EXPORT int rthx_solve_grey(const int64_t* row_ptr, const int32_t* cols, con
     S.op.F = Fd.as<double>();
     S.op.part = S.part.as<double>();
   } else {
-    std::vector<int64_t> rp;
-    std::vector<int32_t> ci;
-    std::vector<double> v;
-    STRY(rthx::gs::csr_transpose(row_ptr, cols, vals, n, rp, ci, v));
-    HIP_TRY(trp.reserve((n + 1) * 8), "hipMalloc");
-    HIP_TRY(tci.reserve(ci.size() * 4), "hipMalloc");
-    HIP_TRY(tv.reserve(v.size() * 8), "hipMalloc");
-    HIP_TRY(hipMemcpyAsync(trp.p, rp.data(), (n + 1) * 8, hipMemcpyHostToDevice, S.s), "hipMemcpy");
-    HIP_TRY(hipMemcpyAsync(tci.p, ci.data(), ci.size() * 4, hipMemcpyHostToDevice, S.s), "hipMemcpy");
-    HIP_TRY(hipMemcpyAsync(tv.p, v.data(), v.size() * 8, hipMemcpyHostToDevice, S.s), "hipMemcpy");
+    RTHX_TRY(T.upload(Ft.rp.data(), Ft.ci.data(), Ft.v.data(), n, Ft.nnz(), S.s));
     HIP_TRY(hipStreamSynchronize(S.s), "upload");
     S.op.dense = false;
-    S.op.rp = trp.as<int64_t>();
-    S.op.ci = tci.as<int32_t>();
-    S.op.v = tv.as<double>();
+    S.op.rp = T.rp.as<int64_t>();
+    S.op.ci = T.ci.as<int32_t>();
+    S.op.v = T.v.as<double>();
   }
   return run(S, coeff, h, args, j_out, g_out, info, t0);
 }
@@ -265,7 +227,7 @@ RTHX_EXPORT int rthx_solve_grey_smoothed(const rthx_smooth_result* F, const doub
                                          rthx_solve_info* info) {
   const double t0 = now_ms();
   if (!F) return fail(RTHX_EINVAL, "null smoothing result");
-  STRY(check_args(F->n, coeff, h, args, j_out, g_out));
+  RTHX_TRY(check_args(F->n, coeff, h, args, j_out, g_out));
   if (args->device != F->device) return fail(RTHX_EINVAL, "args.device differs from the result's device");
   HIP_TRY(hipSetDevice(F->device), "hipSetDevice");
   Solver S;
@@ -279,7 +241,7 @@ RTHX_EXPORT int rthx_solve_grey_smoothed(const rthx_smooth_result* F, const doub
     S.op.part = S.part.as<double>();
   } else {  // F' from the handle's device CSR (formed once, kept in the handle)
     S.op.dense = false;
-    STRY(rthx::tp::smooth_transposed(F, S.s, &S.op.rp, &S.op.ci, &S.op.v));
+    RTHX_TRY(rthx::tp::smooth_transposed(F, S.s, &S.op.rp, &S.op.ci, &S.op.v));
   }
   return run(S, coeff, h, args, j_out, g_out, info, t0);
 }
@@ -289,8 +251,8 @@ RTHX_EXPORT int rthx_solve_grey_result(const rthx_result* counts, int64_t n, con
                                        rthx_solve_info* info) {
   const double t0 = now_ms();
   if (!counts) return fail(RTHX_EINVAL, "null result");
-  STRY(rthx::result_ready(counts));  // (RTHX_ESTATE without a trace; completes a pending one)
-  STRY(check_args(n, coeff, h, args, j_out, g_out));
+  RTHX_TRY(rthx::result_ready(counts));  // (RTHX_ESTATE without a trace; completes a pending one)
+  RTHX_TRY(check_args(n, coeff, h, args, j_out, g_out));
   if (!counts->parts.empty() || counts->device < 0)
     return fail(RTHX_EINVAL, "rthx_solve_grey_result needs a single-device result");
   if (counts->begin != 0 || counts->stride != 1 || n > counts->n_rows || n > counts->N)
@@ -301,8 +263,8 @@ RTHX_EXPORT int rthx_solve_grey_result(const rthx_result* counts, int64_t n, con
   Solver S;
   S.n = n;
   HIP_TRY(rthx::device_stream(counts->device, &S.s), "hipStreamCreate");
-  rthx::tp::Transposed Ft;
-  STRY(rthx::tp::transpose_result_block(counts, n, S.s, Ft));
+  rthx::tp::DeviceCsr Ft;
+  RTHX_TRY(rthx::tp::transpose_result_block(counts, n, S.s, Ft));
   S.op.dense = false;
   S.op.n = n;
   S.op.rp = Ft.rp.as<int64_t>();

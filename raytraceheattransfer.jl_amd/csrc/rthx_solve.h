@@ -6,7 +6,6 @@
 #include <stdint.h>
 
 #include <functional>
-#include <vector>
 
 #include "rthx_common.h"
 
@@ -47,9 +46,6 @@ struct Krylov {
 };
 using Apply = std::function<hipError_t(const double* x, double* out)>;
 int gmres(Krylov& S, const Apply& M, const rthx_solve_args& a, bool warm, rthx_solve_info& info);
-// Host CSR of F -> CSR of F' (validated: RTHX_EINVAL on a malformed matrix).
-int csr_transpose(const int64_t* row_ptr, const int32_t* cols, const double* vals, int64_t n,
-                  std::vector<int64_t>& rp, std::vector<int32_t>& ci, std::vector<double>& v);
 
 }  // namespace gs
 }  // namespace rthx

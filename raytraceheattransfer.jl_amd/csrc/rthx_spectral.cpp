@@ -7,7 +7,8 @@
 // system in the stacked radiosities per outer iteration, solved by the
 // restarted GMRES of rthx_solve.cpp (warm-started), and the outer loop only
 // refreshes the emission fractions f(T).  All arguments are validated on the
-// host before the first GPU call.
+// host before the first GPU call; a sparse band is checked and transposed
+// there by rthx_csr_host.h and uploaded as a tp::DeviceCsr (rthx_transpose.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,18 +29,7 @@ using rthx::now_ms;
 
 namespace {
 
-#define STRY(expr)                  \
-  do {                              \
-    int _rc = (expr);               \
-    if (_rc != RTHX_OK) return _rc; \
-  } while (0)
-
-// F' of one sparse band on the host (validated), ready for upload.
-struct HostCsr {
-  std::vector<int64_t> rp;
-  std::vector<int32_t> ci;
-  std::vector<double> v;
-};
+using HostCsr = rthx::csr::Host;  // F' of one sparse band on the host (validated), ready for upload
 
 bool all_finite(const double* a, int64_t count) {
   for (int64_t i = 0; i < count; ++i)
@@ -78,18 +68,10 @@ int check_bands(const rthx_spectral_band* F, int32_t n_mats, int64_t n, int32_t 
     } else if (F[k].dense) {
       if (!all_finite(F[k].dense, n * n)) return fail(RTHX_EINVAL, "non-finite F entry");
     } else {
-      STRY(rthx::gs::csr_transpose(F[k].row_ptr, F[k].cols, F[k].vals, n, csr[k].rp, csr[k].ci, csr[k].v));
+      RTHX_TRY(rthx::check_host_csr(F[k].row_ptr, F[k].cols, F[k].vals, n, n, false, false));
+      rthx::csr::transposed(F[k].row_ptr, F[k].cols, F[k].vals, n, n, csr[k]);
     }
   }
-  return RTHX_OK;
-}
-
-int open_device(int32_t device, hipStream_t* s) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(RTHX_EDEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(RTHX_EINVAL, "device ordinal out of range");
-  HIP_TRY(hipSetDevice(device), "hipSetDevice");
-  HIP_TRY(rthx::device_stream(device, s), "hipStreamCreate");
   return RTHX_OK;
 }
 
@@ -102,12 +84,13 @@ int upload(DevBuf& d, const void* src, size_t bytes, hipStream_t s) {
 // The band matrices on the device and the launch description of the operator.
 struct Operator {
   std::vector<std::unique_ptr<DevBuf>> bufs;
+  std::vector<std::unique_ptr<rthx::tp::DeviceCsr>> sparse;
   DevBuf mats, part;
   rthx::sp::BandedOp op;
 
   int put(const void* src, size_t bytes, hipStream_t s, void** out) {
     bufs.emplace_back(new DevBuf);
-    STRY(upload(*bufs.back(), src, bytes, s));
+    RTHX_TRY(upload(*bufs.back(), src, bytes, s));
     *out = bufs.back()->p;
     return RTHX_OK;
   }
@@ -121,26 +104,26 @@ struct Operator {
     for (int k = 0; k < n_mats; ++k) {
       void* p = nullptr;
       if (F[k].smoothed && !F[k].smoothed->dense) {  // F' from the handle's device CSR
-        STRY(rthx::tp::smooth_transposed(F[k].smoothed, s, &host[k].rp, &host[k].ci, &host[k].v));
+        RTHX_TRY(rthx::tp::smooth_transposed(F[k].smoothed, s, &host[k].rp, &host[k].ci, &host[k].v));
         op.any_sparse = true;
       } else if (F[k].smoothed) {
         host[k].F = F[k].smoothed->F.as<double>();
         op.any_dense = true;
       } else if (F[k].dense) {
-        STRY(put(F[k].dense, (size_t)n * n * 8, s, &p));
+        RTHX_TRY(put(F[k].dense, (size_t)n * n * 8, s, &p));
         host[k].F = static_cast<const double*>(p);
         op.any_dense = true;
       } else {
-        STRY(put(csr[k].rp.data(), csr[k].rp.size() * 8, s, &p));
-        host[k].rp = static_cast<const int64_t*>(p);
-        STRY(put(csr[k].ci.data(), csr[k].ci.size() * 4, s, &p));
-        host[k].ci = static_cast<const int32_t*>(p);
-        STRY(put(csr[k].v.data(), csr[k].v.size() * 8, s, &p));
-        host[k].v = static_cast<const double*>(p);
+        sparse.emplace_back(new rthx::tp::DeviceCsr);
+        rthx::tp::DeviceCsr& T = *sparse.back();
+        RTHX_TRY(T.upload(csr[k].rp.data(), csr[k].ci.data(), csr[k].v.data(), n, csr[k].nnz(), s));
+        host[k].rp = T.rp.as<int64_t>();
+        host[k].ci = T.ci.as<int32_t>();
+        host[k].v = T.v.as<double>();
         op.any_sparse = true;
       }
     }
-    STRY(upload(mats, host.data(), host.size() * sizeof(rthx::sp::BandMat), s));
+    RTHX_TRY(upload(mats, host.data(), host.size() * sizeof(rthx::sp::BandMat), s));
     HIP_TRY(hipStreamSynchronize(s), "upload");
     op.mats = mats.as<rthx::sp::BandMat>();
     op.shared_F = n_mats == 1 ? host[0].F : nullptr;
@@ -156,19 +139,15 @@ struct Operator {
 // a stream synchronisation (a norm or a Hessenberg column read back) before
 // the next one, so the pending pair is complete when it is read.
 struct ApplyTimer {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  rthx::EventPair ev;
   bool pending = false;
   double ms = 0.0;
-  ~ApplyTimer() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
   hipError_t collect() {
     if (!pending) return hipSuccess;
-    hipError_t e = hipEventSynchronize(e1);
+    hipError_t e = hipEventSynchronize(ev.e[1]);
     if (e != hipSuccess) return e;
     float t = 0.f;
-    e = hipEventElapsedTime(&t, e0, e1);
+    e = ev.elapsed(&t);
     if (e != hipSuccess) return e;
     ms += t;
     pending = false;
@@ -188,11 +167,11 @@ RTHX_EXPORT int rthx_solve_spectral(const rthx_spectral_band* F, int32_t n_matri
   const double t0 = now_ms();
   if (!F || !b || !prop || !size || !T_in || !q_in || !args || !j_out || !g_out || !T_out || !e_out)
     return fail(RTHX_EINVAL, "bad spectral solve arguments");
-  STRY(check_sizes(n, n_bands, n_matrices));
+  RTHX_TRY(check_sizes(n, n_bands, n_matrices));
   if (!(args->rtol >= 0) || !(args->atol >= 0) || args->memory < 1 || args->max_outer < 1 ||
       !(args->convergence_tol >= 0))
     return fail(RTHX_EINVAL, "bad tolerances");
-  STRY(check_limits(band_limits, n_bands));
+  RTHX_TRY(check_limits(band_limits, n_bands));
   const int K = n_bands;
   const int64_t N = (int64_t)K * n;
   if (!all_finite(b, N) || !all_finite(prop, N) || !all_finite(size, n) || !all_finite(T_in, n) ||
@@ -212,25 +191,25 @@ RTHX_EXPORT int rthx_solve_spectral(const rthx_spectral_band* F, int32_t n_matri
   const double t_start = t_max > 0.0 ? t_max : 1000.0;  // first iterate of the unknown temperatures
   for (int64_t i = 0; i < n; ++i) T0[i] = radeq[i] ? t_start : T_in[i];
   std::vector<HostCsr> csr;
-  STRY(check_bands(F, n_matrices, n, args->device, csr));
+  RTHX_TRY(check_bands(F, n_matrices, n, args->device, csr));
 
   hipStream_t s = nullptr;
-  STRY(open_device(args->device, &s));
+  RTHX_TRY(rthx::open_device(args->device, &s));
   Operator A;
-  STRY(A.setup(F, n_matrices, n, K, csr, s));
+  RTHX_TRY(A.setup(F, n_matrices, n, K, csr, s));
   gs::Krylov S;
   S.s = s;
   S.n = N;
-  STRY(S.reserve(args->memory));
+  RTHX_TRY(S.reserve(args->memory));
   DevBuf db, dprop, dsize, dTin, dq, dradeq, dlim, dT, de, df, dplain, dg, dprev;
-  STRY(upload(db, b, N * 8, s));
-  STRY(upload(dprop, prop, N * 8, s));
-  STRY(upload(dsize, size, n * 8, s));
-  STRY(upload(dTin, T_in, n * 8, s));
-  STRY(upload(dq, q_in, n * 8, s));
-  STRY(upload(dradeq, radeq.data(), n, s));
-  STRY(upload(dlim, band_limits, (size_t)(K + 1) * 8, s));
-  STRY(upload(dT, T0.data(), n * 8, s));
+  RTHX_TRY(upload(db, b, N * 8, s));
+  RTHX_TRY(upload(dprop, prop, N * 8, s));
+  RTHX_TRY(upload(dsize, size, n * 8, s));
+  RTHX_TRY(upload(dTin, T_in, n * 8, s));
+  RTHX_TRY(upload(dq, q_in, n * 8, s));
+  RTHX_TRY(upload(dradeq, radeq.data(), n, s));
+  RTHX_TRY(upload(dlim, band_limits, (size_t)(K + 1) * 8, s));
+  RTHX_TRY(upload(dT, T0.data(), n * 8, s));
   HIP_TRY(de.reserve(n * 8), "hipMalloc");
   HIP_TRY(df.reserve(N * 8), "hipMalloc");
   HIP_TRY(dplain.reserve(N * 8), "hipMalloc");
@@ -251,14 +230,13 @@ RTHX_EXPORT int rthx_solve_spectral(const rthx_spectral_band* F, int32_t n_matri
   double* sm = S.small.as<double>();
 
   ApplyTimer timer;
-  HIP_TRY(hipEventCreate(&timer.e0), "hipEventCreate");
-  HIP_TRY(hipEventCreate(&timer.e1), "hipEventCreate");
+  HIP_TRY(timer.ev.create(), "hipEventCreate");
   auto timed_apply = [&](const double* in, double* out) -> hipError_t {
     hipError_t e = timer.collect();
     if (e != hipSuccess) return e;
-    if ((e = hipEventRecord(timer.e0, s)) != hipSuccess) return e;
+    if ((e = timer.ev.start(s)) != hipSuccess) return e;
     if ((e = sp::apply(A.op, in, pb, pf, pre, pg, out, s)) != hipSuccess) return e;
-    if ((e = hipEventRecord(timer.e1, s)) != hipSuccess) return e;
+    if ((e = timer.ev.stop(s)) != hipSuccess) return e;
     timer.pending = true;
     return hipSuccess;
   };
@@ -281,7 +259,7 @@ RTHX_EXPORT int rthx_solve_spectral(const rthx_spectral_band* F, int32_t n_matri
     HIP_TRY(sp::rhs(pf, pe, dq.as<double>(), pre, n, K, S.h.as<double>(), s), "rhs");
     HIP_TRY(hipMemcpyAsync(dprev.p, x, N * 8, hipMemcpyDeviceToDevice, s), "hipMemcpy");
     rthx_solve_info L{};
-    STRY(gs::gmres(S, M, sa, outer > 1, L));
+    RTHX_TRY(gs::gmres(S, M, sa, outer > 1, L));
     I.outer_iterations = outer;
     I.gmres_iterations += L.iterations;
     I.residual = L.residual;
@@ -294,7 +272,7 @@ RTHX_EXPORT int rthx_solve_spectral(const rthx_spectral_band* F, int32_t n_matri
     HIP_TRY(sp::temperatures(plim, K, pprop, dsize.as<double>(), dTin.as<double>(), pre, true, n, pe, pT, s),
             "temperatures");
     double d[2];
-    STRY(S.d2h(d, sm, 2));
+    RTHX_TRY(S.d2h(d, sm, 2));
     I.change = d[1] > 0.0 ? std::sqrt(d[0] / d[1]) : 0.0;
     // converged: the reference's criterion, or a warm start that already
     // solves the system of the refreshed fractions (GMRES took no step)
@@ -304,10 +282,10 @@ RTHX_EXPORT int rthx_solve_spectral(const rthx_spectral_band* F, int32_t n_matri
     }
   }
   HIP_TRY(timer.collect(), "hipEventElapsedTime");
-  STRY(S.d2h(j_out, x, N));
-  STRY(S.d2h(g_out, pg, N));
-  STRY(S.d2h(T_out, pT, n));
-  STRY(S.d2h(e_out, pe, n));
+  RTHX_TRY(S.d2h(j_out, x, N));
+  RTHX_TRY(S.d2h(g_out, pg, N));
+  RTHX_TRY(S.d2h(T_out, pT, n));
+  RTHX_TRY(S.d2h(e_out, pe, n));
   I.ms_apply = timer.ms;
   I.ms_total = now_ms() - t0;
   if (info) *info = I;
@@ -318,25 +296,25 @@ RTHX_EXPORT int rthx_spectral_apply(const rthx_spectral_band* F, int32_t n_matri
                                     int32_t device, const double* x, const double* b, const double* f,
                                     const uint8_t* is_radeq, double* g_out, double* y_out) {
   if (!F || !x || !g_out || (y_out && (!b || !f))) return fail(RTHX_EINVAL, "bad spectral apply arguments");
-  STRY(check_sizes(n, n_bands, n_matrices));
+  RTHX_TRY(check_sizes(n, n_bands, n_matrices));
   const int64_t N = (int64_t)n_bands * n;
   if (!all_finite(x, N) || (y_out && (!all_finite(b, N) || !all_finite(f, N))))
     return fail(RTHX_EINVAL, "non-finite input");
   std::vector<HostCsr> csr;
-  STRY(check_bands(F, n_matrices, n, device, csr));
+  RTHX_TRY(check_bands(F, n_matrices, n, device, csr));
   hipStream_t s = nullptr;
-  STRY(open_device(device, &s));
+  RTHX_TRY(rthx::open_device(device, &s));
   Operator A;
-  STRY(A.setup(F, n_matrices, n, n_bands, csr, s));
+  RTHX_TRY(A.setup(F, n_matrices, n, n_bands, csr, s));
   DevBuf dx, db, df, dre, dg, dy;
-  STRY(upload(dx, x, N * 8, s));
+  RTHX_TRY(upload(dx, x, N * 8, s));
   HIP_TRY(dg.reserve(N * 8), "hipMalloc");
   std::vector<uint8_t> none;
   if (y_out) {
-    STRY(upload(db, b, N * 8, s));
-    STRY(upload(df, f, N * 8, s));
+    RTHX_TRY(upload(db, b, N * 8, s));
+    RTHX_TRY(upload(df, f, N * 8, s));
     if (!is_radeq) none.assign(n, 0);
-    STRY(upload(dre, is_radeq ? is_radeq : none.data(), n, s));
+    RTHX_TRY(upload(dre, is_radeq ? is_radeq : none.data(), n, s));
     HIP_TRY(dy.reserve(N * 8), "hipMalloc");
   }
   HIP_TRY(rthx::sp::apply(A.op, dx.as<double>(), db.as<double>(), df.as<double>(), dre.as<uint8_t>(), dg.as<double>(),
@@ -352,16 +330,16 @@ RTHX_EXPORT int rthx_spectral_fractions(const double* band_limits, int32_t n_ban
                                         const double* prop, int64_t n, int32_t device, double* plain_out,
                                         double* weighted_out) {
   if (!T || !plain_out) return fail(RTHX_EINVAL, "bad spectral fractions arguments");
-  STRY(check_sizes(n, n_bands, 1));
-  STRY(check_limits(band_limits, n_bands));
+  RTHX_TRY(check_sizes(n, n_bands, 1));
+  RTHX_TRY(check_limits(band_limits, n_bands));
   const int64_t N = (int64_t)n_bands * n;
   if (prop && !all_finite(prop, N)) return fail(RTHX_EINVAL, "non-finite input");
   hipStream_t s = nullptr;
-  STRY(open_device(device, &s));
+  RTHX_TRY(rthx::open_device(device, &s));
   DevBuf dlim, dT, dprop, dplain, dw;
-  STRY(upload(dlim, band_limits, (size_t)(n_bands + 1) * 8, s));
-  STRY(upload(dT, T, n * 8, s));
-  if (prop) STRY(upload(dprop, prop, N * 8, s));
+  RTHX_TRY(upload(dlim, band_limits, (size_t)(n_bands + 1) * 8, s));
+  RTHX_TRY(upload(dT, T, n * 8, s));
+  if (prop) RTHX_TRY(upload(dprop, prop, N * 8, s));
   HIP_TRY(dplain.reserve(N * 8), "hipMalloc");
   if (weighted_out) HIP_TRY(dw.reserve(N * 8), "hipMalloc");
   HIP_TRY(rthx::sp::fractions(dlim.as<double>(), n_bands, dT.as<double>(), prop ? dprop.as<double>() : nullptr, n,
@@ -383,22 +361,22 @@ RTHX_EXPORT int rthx_debug_spectral_apply_times(const rthx_spectral_band* F, int
                                                 int32_t reps, double* ms_out) {
   if (!F || !ms_out || reps < 1 || warmup < 0 || (mode != 0 && mode != 1))
     return fail(RTHX_EINVAL, "bad apply timing arguments");
-  STRY(check_sizes(n, n_bands, n_matrices));
+  RTHX_TRY(check_sizes(n, n_bands, n_matrices));
   std::vector<HostCsr> csr;
-  STRY(check_bands(F, n_matrices, n, device, csr));
+  RTHX_TRY(check_bands(F, n_matrices, n, device, csr));
   hipStream_t s = nullptr;
-  STRY(open_device(device, &s));
+  RTHX_TRY(rthx::open_device(device, &s));
   Operator A;
-  STRY(A.setup(F, n_matrices, n, n_bands, csr, s));
+  RTHX_TRY(A.setup(F, n_matrices, n, n_bands, csr, s));
   if (mode == 1 && A.op.any_sparse) return fail(RTHX_EINVAL, "sequential grey applies: dense matrices only");
   const int64_t N = (int64_t)n_bands * n;
   std::vector<double> half(N, 0.5);
   std::vector<uint8_t> ones(n, 1);
   DevBuf dx, db, df, dre, dg, dy, gpart;
-  STRY(upload(dx, half.data(), N * 8, s));
-  STRY(upload(db, half.data(), N * 8, s));
-  STRY(upload(df, half.data(), N * 8, s));
-  STRY(upload(dre, ones.data(), n, s));
+  RTHX_TRY(upload(dx, half.data(), N * 8, s));
+  RTHX_TRY(upload(db, half.data(), N * 8, s));
+  RTHX_TRY(upload(df, half.data(), N * 8, s));
+  RTHX_TRY(upload(dre, ones.data(), n, s));
   HIP_TRY(dg.reserve(N * 8), "hipMalloc");
   HIP_TRY(dy.reserve(N * 8), "hipMalloc");
   HIP_TRY(gpart.reserve((size_t)rthx::gs::part_doubles(n) * 8), "hipMalloc");

@@ -42,9 +42,9 @@ hipError_t write(const Pair& J, const double* w, const uint32_t* mark, const int
 // Device memory of one build: A', the transpose's scratch, mark and len
 // (freed when it goes out of scope).
 struct Work {
-  tp::Plan P;
-  tp::Transposed T;
-  DevBuf tscratch, mark, len;
+  tp::Scratch ts;
+  tp::DeviceCsr T;
+  DevBuf mark, len;
 };
 
 // Allocates what a build over A needs (no launch).

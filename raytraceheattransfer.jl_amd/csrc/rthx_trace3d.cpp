@@ -820,10 +820,7 @@ RTHX_EXPORT int rthx_scene3d_create_grouped(const double* xyz, const int32_t* nv
   rthx::fill_tables(tables.data());
 
   const double t_bvh = now_ms();
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(RTHX_EDEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(RTHX_EINVAL, "device ordinal out of range");
-  HIP_TRY(hipSetDevice(device), "hipSetDevice");
+  RTHX_TRY(rthx::open_device(device, nullptr));  // (the stream: below, once the handle exists)
   rthx_scene3d* s = new (std::nothrow) rthx_scene3d();
   if (!s) return fail(RTHX_ENOMEM, "host allocation failed");
   s->device = device;

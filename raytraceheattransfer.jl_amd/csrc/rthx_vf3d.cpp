@@ -81,12 +81,8 @@ RTHX_EXPORT int rthx_view_factors_3d(const double* xyz, const int32_t* nv, int64
     if (info) *info = inf;
     return RTHX_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(RTHX_EDEVICE, "no HIP device visible");
-  if (a->device < 0 || a->device >= ndev) return fail(RTHX_EINVAL, "device ordinal out of range");
-  HIP_TRY(hipSetDevice(a->device), "hipSetDevice");
   hipStream_t st = nullptr;
-  HIP_TRY(rthx::device_stream(a->device, &st), "hipStreamCreate");
+  RTHX_TRY(rthx::open_device(a->device, &st));
   hipEvent_t e0 = nullptr, e1 = nullptr;
   DevBuf d_polys, d_area, d_F;
   int rc = RTHX_OK;
