@@ -320,6 +320,23 @@ __host__ __device__ __forceinline__ double sconst(double c) {
   return c;
 }
 
+// fma(z, c1, c2) for two polynomial constants (the innermost step of a Horner
+// chain), written as the instruction (device code).  gfx9's VOP3 reads one
+// scalar operand, so one constant sits in a scalar pair (c2) and the other
+// in a VGPR pair that the compiler sets once ahead of the ray loop (c1).
+// Left to itself the compiler picks the destructive v_fmac_f64 for this step
+// and copies c2 into its accumulator for every ray (one v_mov_b64 a step).
+// The same operation on the same operands: one IEEE fma.
+__host__ __device__ __forceinline__ double fma_cc(double z, double c1, double c2) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double d;
+  __asm__("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(c1), "v"(z), "s"(c2));
+  return d;
+#else
+  return __builtin_fma(z, c1, c2);
+#endif
+}
+
 // -ln(u) for u in (0, 1] from a 128-entry table (the free path
 // S = -ln(u)/beta, traceRay.jl:25,79).  u = 2^k z with z in [0.6875, 1.375)
 // (so u near 1 keeps k = 0), table entry i = 7 bits of z below the exponent:
@@ -357,15 +374,21 @@ __host__ __device__ __forceinline__ double neg_log_tab(double u, const double* t
 // and only k moves by 32 (an integer subtract instead of v_ldexp_f64).
 // Bit-identical to neg_log_tab(u32(w)) for every w (w = 0 -> +inf).
 __host__ __device__ __forceinline__ double neg_log_u32(uint32_t w, const double* tab) {
+  // The low word of kLogOff and of the exponent mask is zero, so tmp's low
+  // word is ix's and every step below is neg_log_tab's on the high word
+  // alone: no borrow, no 64-bit subtract, and a table offset that is 32-bit
+  // from the start (the load takes the scalar base, as cos_2pi_u32's).
+  static_assert((uint32_t)kLogOff == 0u, "the high-word form needs a zero low word");
   const uint64_t ix = dbits((double)w);
-  const uint64_t tmp = ix - kLogOff;
-  const int i = (int)((tmp >> 45) & (kLogTable - 1));
-  const int32_t k = ((int32_t)(uint32_t)(tmp >> 32) >> 20) - 32;
-  const double z = bitsd(ix - (tmp & 0xFFF0000000000000ull));
-  const double* const te = (const double*)((const char*)tab + ((uint32_t)i << 5));  // (a 32-bit byte offset on the base)
+  const uint32_t ix_hi = (uint32_t)(ix >> 32);
+  const uint32_t tmp_hi = ix_hi - (uint32_t)(kLogOff >> 32);
+  const uint32_t i32 = ((tmp_hi >> 13) & (uint32_t)(kLogTable - 1)) << 5;  // entry i's byte offset
+  const int32_t k = ((int32_t)tmp_hi >> 20) - 32;
+  const double z = bitsd(((uint64_t)(ix_hi - (tmp_hi & 0xFFF00000u)) << 32) | (uint32_t)ix);
+  const double* const te = (const double*)((const char*)tab + i32);  // (a 32-bit byte offset on the base)
   const double invc = te[0], t_hi = te[1], t_lo = te[2];
   const double r = __builtin_fma(z, invc, -1.0);
-  double q = __builtin_fma(r, 1.0 / 7.0, -1.0 / 6.0);
+  double q = fma_cc(r, 1.0 / 7.0, -1.0 / 6.0);
   q = __builtin_fma(r, q, sconst(1.0 / 5.0));
   q = __builtin_fma(r, q, -1.0 / 4.0);
   q = __builtin_fma(r, q, sconst(1.0 / 3.0));
@@ -425,8 +448,8 @@ __device__ __forceinline__ double cos_2pi_u32(uint32_t w, const double* tab) {
   const int j = (int)(w >> 24);
   const double d = (double)(w & 0xFFFFFFu) * (RTHX_TWO_PI * 0x1.0p-32);
   const double z = d * d;
-  const double cd = __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, -1.0 / 720.0, 1.0 / 24.0), -0.5), 1.0);
-  const double ps = __builtin_fma(z, __builtin_fma(z, -1.0 / 5040.0, 1.0 / 120.0), sconst(-1.0 / 6.0));
+  const double cd = __builtin_fma(z, __builtin_fma(z, fma_cc(z, -1.0 / 720.0, 1.0 / 24.0), -0.5), 1.0);
+  const double ps = __builtin_fma(z, fma_cc(z, -1.0 / 5040.0, 1.0 / 120.0), sconst(-1.0 / 6.0));
   const double sd = __builtin_fma(d * z, ps, d);
   // the (cos, sin) pair in one 16-byte load; 8-byte aligned only, because a
   // bin's table block is an odd number of doubles (kLdsTableDoubles)
