@@ -214,6 +214,60 @@ extern "C" __attribute__((visibility("default"))) int rthx_debug_neg_log_u32(con
   return 0;
 }
 
+// Host evaluation of the box walls' candidacy test (wall_candidate,
+// rthx_device.h) beside the two forms it stands for: form 0 the shipped
+// predicate, 1 the product form |s| |d| > 0 of earlier versions, 2 the
+// reference's quotient form |s| / |d| > 0, each with |d| >= 1e-10.
+extern "C" __attribute__((visibility("default"))) int rthx_debug_wall_candidate(double s, double d, int32_t form) {
+  const double as = std::fabs(s), ad = std::fabs(d);
+  switch (form) {
+    case 0: return rthx::wall_candidate(s, d) ? 1 : 0;
+    case 1: return (ad >= 1e-10 && as * ad > 0.0) ? 1 : 0;
+    case 2: return (as / ad > 0.0 && ad >= 1e-10) ? 1 : 0;
+    default: return -1;
+  }
+}
+
+// The theta draw's sine on the device (sin_theta_u32, rthx_device.h), for
+// tests.  The sweep compares it with the earlier expression
+// 2.0 * sqrt_unit(u (1 - u)) on the n words from w_begin (w_begin + n <= 2^32)
+// and returns the number of words whose bits differ and the least of them
+// (2^64 - 1 if none); rthx_debug_sin_theta returns the values for given words.
+extern "C" __attribute__((visibility("default"))) int rthx_debug_sin_theta_sweep(int32_t device, uint32_t w_begin,
+                                                                                 uint64_t n, uint64_t* n_diff,
+                                                                                 uint64_t* first_diff) {
+  if (!n_diff || !first_diff) return fail(RTHX_EINVAL, "null output");
+  if ((uint64_t)w_begin + n > (1ull << 32)) return fail(RTHX_EINVAL, "word range past 2^32");
+  hipStream_t stream = nullptr;
+  RTHX_TRY(rthx::open_device(device, &stream));
+  DevBuf buf;
+  HIP_TRY(buf.reserve(2 * sizeof(unsigned long long)), "hipMalloc (sin theta sweep)");
+  unsigned long long h[2] = {0ull, ~0ull};
+  HIP_TRY(hipMemcpyAsync(buf.p, h, sizeof(h), hipMemcpyHostToDevice, stream), "hipMemcpy (sin theta sweep)");
+  HIP_TRY(rthx::launch_sin_theta_sweep(w_begin, n, (unsigned long long*)buf.p, stream), "sin_theta_sweep_kernel");
+  HIP_TRY(hipMemcpyAsync(h, buf.p, sizeof(h), hipMemcpyDeviceToHost, stream), "hipMemcpy (sin theta sweep)");
+  HIP_TRY(hipStreamSynchronize(stream), "hipStreamSynchronize (sin theta sweep)");
+  *n_diff = h[0];
+  *first_diff = h[1];
+  return RTHX_OK;
+}
+
+extern "C" __attribute__((visibility("default"))) int rthx_debug_sin_theta(int32_t device, const uint32_t* words,
+                                                                           int64_t n, double* out) {
+  if (n < 0 || ((!words || !out) && n > 0)) return fail(RTHX_EINVAL, "null or negative argument");
+  if (n == 0) return RTHX_OK;
+  hipStream_t stream = nullptr;
+  RTHX_TRY(rthx::open_device(device, &stream));
+  DevBuf dw, dout;
+  HIP_TRY(dw.reserve((size_t)n * sizeof(uint32_t)), "hipMalloc (sin theta)");
+  HIP_TRY(dout.reserve((size_t)n * sizeof(double)), "hipMalloc (sin theta)");
+  HIP_TRY(hipMemcpyAsync(dw.p, words, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, stream), "hipMemcpy (sin theta)");
+  HIP_TRY(rthx::launch_sin_theta((const uint32_t*)dw.p, n, (double*)dout.p, stream), "sin_theta_kernel");
+  HIP_TRY(hipMemcpyAsync(out, dout.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream), "hipMemcpy (sin theta)");
+  HIP_TRY(hipStreamSynchronize(stream), "hipStreamSynchronize (sin theta)");
+  return RTHX_OK;
+}
+
 RTHX_EXPORT int rthx_abi_version(void) { return RTHX_ABI_VERSION; }
 
 RTHX_EXPORT const char* rthx_last_error(void) { return rthx::g_last_error.c_str(); }

@@ -438,6 +438,45 @@ __device__ __forceinline__ double sqrt_unit(double x) {
   return g;
 }
 
+// sin(theta) of the isotropic draw theta = acos(1 - 2u), u = w 2^-32
+// (emitVolumeRay2D.jl:26-31, isotropicScatter2D.jl:1-4):
+// sin(acos(x)) = sqrt((1 - x)(1 + x)) = 2 sqrt(u (1 - u)), bit for bit the
+// value of 2.0 * sqrt_unit(RN(u (1 - u))) (sin_theta_parent, the expression
+// of earlier versions, kept for the exhaustive comparison of
+// rthx_debug_sin_theta_sweep), in fewer fp64 instructions:
+//  - the root is taken of 4 u (1 - u) <= 1.  RN(1 - u) is exact (32 bits) and
+//    lies in [2^-32, 1]; scaled by 2^-30 instead of 2^-32 it makes
+//    w om = 4 RN(u (1 - u)), and a power of two commutes with the product's
+//    rounding and with the root's, so the final doubling is gone;
+//  - the scaling is a subtraction of 30 from the exponent field on the high
+//    word (the scaled value is at least 2^-62, normal), a 32-bit add in place
+//    of v_ldexp_f64;
+//  - one correction step after the coupled iteration, not sqrt_unit's two.
+//    The second makes the root correctly rounded for every double; the 2^32
+//    arguments here are already there after the first, which is a property of
+//    gfx950's v_rsq_f64 and was settled by enumeration: 0 of 2^32 words differ
+//    (tests/test_wall_candidate.py runs the sweep).  Every other root keeps
+//    sqrt_unit.
+__device__ __forceinline__ double sin_theta_parent(uint32_t w) {
+  const double wd = (double)w;
+  return 2.0 * sqrt_unit(wd * (__builtin_fma(wd, -0x1.0p-32, 1.0) * 0x1.0p-32));
+}
+
+__device__ __forceinline__ double sin_theta_u32(uint32_t w) {
+  const double wd = (double)w;
+  const uint64_t ob = dbits(__builtin_fma(wd, -0x1.0p-32, 1.0));  // RN(1 - u)
+  const double om = bitsd(((uint64_t)((uint32_t)(ob >> 32) - (30u << 20)) << 32) | (uint32_t)ob);
+  const double x = wd * om;
+  // (x = 0, the word 0, takes the finite estimate and yields 0, as in sqrt_unit)
+  const double y = __builtin_amdgcn_rsq(__builtin_fmax(x, 0x1.0p-1000));
+  double g = x * y, h = 0.5 * y;
+  const double r = __builtin_fma(-h, g, 0.5);
+  g = __builtin_fma(g, r, g);
+  h = __builtin_fma(h, r, h);
+  const double d = __builtin_fma(-g, g, x);
+  return __builtin_fma(d, h, g);
+}
+
 // cos(2 pi w / 2^32) for a 32-bit draw w (emitVolumeRay2D.jl:28-31: phi = 2 pi u,
 // cos(phi)).  Table-and-polynomial: w = j 2^24 + m, with (cos, sin) of
 // 2 pi j/256 from `tab` and d = 2 pi m/2^32 < 2 pi/256, so cos(a + d) =
@@ -543,12 +582,31 @@ struct BoxHit {
   bool any;
 };
 
+// A wall of the box holding the point, on the side d points to, is a
+// candidate when its parameter |s| / |d| is positive and |d| >= 1e-10
+// (distToSurface2D.jl:8-12; s = bound - coordinate, so num den = |s| |d|).
+// Given |d| >= 1e-10 > 2^-34 the quotient is positive exactly when s != 0, so
+// no product or quotient is formed.  The product form |s| |d| > 0 gives the
+// same answer unless the product underflows to 0, which needs
+// 0 < |s| < 2^-1040: s is a difference of a bound and a coordinate, and a
+// non-zero difference that small needs both below 2^-988, a range div_pos
+// already excludes.  There this form is the reference's (quotient > 0) and
+// the product form is not.  (|s| > 0, not s != 0: false for a NaN, as both
+// other forms.)
+__host__ __device__ __forceinline__ bool wall_candidate(double s, double d) {
+  return (__builtin_fabs(d) >= 1e-10) & (__builtin_fabs(s) > 0.0);
+}
+
 __device__ __forceinline__ BoxHit box_hit_in(double px, double py, double dx, double dy, double xb, double yb) {
   const bool xdn = dx < 0.0, ydn = dy < 0.0;
   // (the magnitudes enter every product as operand modifiers; the winner's
   // num and den are selected signed, so no |x| is formed in a register)
   const double sx = xb - px, sy = yb - py;
-  // (num den > 0: den = |d| on the chosen side, > 0 unless d is 0 there)
+  // (num den > 0: den = |d| on the chosen side, > 0 unless d is 0 there.
+  // The product form stays here: with wall_candidate the MLAT walks of the
+  // C5 bands, which call this per segment, measured 1.3 to 1.9 % slower
+  // (profiles/round17/INDEX.md); the two forms agree wherever |s| is outside
+  // (0, 2^-1040), see wall_candidate.)
   const bool vx = fabs(dx) >= 1e-10 && __dmul_rn(fabs(sx), fabs(dx)) > 0.0;
   const bool vy = fabs(dy) >= 1e-10 && __dmul_rn(fabs(sy), fabs(dy)) > 0.0;
   // wall order: the y wall comes first unless it is the top wall (2) and the
@@ -828,8 +886,8 @@ __device__ __forceinline__ void iso_dir(uint32_t w_th, uint32_t w_ph, const doub
     ct = cos(theta);
     cphi = cos(RTHX_TWO_PI * u32(w_ph));
   } else {
-    ct = 2.0 * u - 1.0;                           // cos(acos(x)) = x
-    st = 2.0 * sqrt_unit(__dmul_rn(u, 1.0 - u));  // sin(acos(x)) = sqrt((1-x)(1+x))
+    ct = 2.0 * u - 1.0;          // cos(acos(x)) = x
+    st = sin_theta_u32(w_th);    // (RN(u (1 - u)) = RN(w RN(1 - u)) 2^-32: the same product from the word)
     cphi = cos_2pi_u32(w_ph, cos_tab);
   }
   dx = __dmul_rn(st, cphi);
@@ -916,15 +974,9 @@ __device__ __forceinline__ void emit_volume(const Emitter& e, double eta, const 
     cphi = cos(RTHX_TWO_PI * u32(rw.a[3]));
   } else {
     // u4 = u32(a2) without forming it: ct = 1 - 2 u4 = fma(w, -2^-31, 1) and
-    // u4 (1 - u4) = w ((1 - u4) 2^-32), the factor an exact power-of-two
-    // scaling of RN(1 - u4) -- the same values as from u4.  (RN(1 - u4) is
-    // formed against the inline constant 1.0 and then scaled by a literal:
-    // fma(w, -2^-64, 2^-32) needed the addend 2^-32 moved into a VGPR pair
-    // for every ray.)
-    const double w4 = (double)rw.a[2];
-    ct = __builtin_fma(w4, -0x1.0p-31, 1.0);           // cos(acos(x)) = x
-    const double om = __builtin_fma(w4, -0x1.0p-32, 1.0) * 0x1.0p-32;
-    st = 2.0 * sqrt_unit(w4 * om);                      // sin(acos(x)) = sqrt((1-x)(1+x))
+    // st from the word (sin_theta_u32) -- the same values as from u4.
+    ct = __builtin_fma((double)rw.a[2], -0x1.0p-31, 1.0);  // cos(acos(x)) = x
+    st = sin_theta_u32(rw.a[2]);
     cphi = cos_2pi_u32(rw.a[3], cos_tab);
   }
   dx = __dmul_rn(st, cphi);
@@ -1232,9 +1284,7 @@ __device__ __forceinline__ int lat_ray_fast(const DevDomain& D, double eta, cons
     // dist_in_box / box_hit_in, the division unconditional
     const double xb = xdn ? cx0 : cx1, yb = ydn ? cy0 : cy1;
     const double sx = xb - ox, sy = yb - oy;
-    const double mx = __dmul_rn(fabs(sx), fabs(dx)), my = __dmul_rn(fabs(sy), fabs(dy));
-    const bool vx = (fabs(dx) >= 1e-10) & (mx > 0.0);
-    const bool vy = (fabs(dy) >= 1e-10) & (my > 0.0);
+    const bool vx = wall_candidate(sx, dx), vy = wall_candidate(sy, dy);
     const double cx = __dmul_rn(fabs(sx), fabs(dy)), cy = __dmul_rn(fabs(sy), fabs(dx));
     const bool xw = vx & (!vy | (y_first & (cx < cy)) | (!y_first & !(cy < cx)));
     const bool any = vx | vy;
@@ -1270,9 +1320,7 @@ __device__ __forceinline__ int lat_ray_fast(const DevDomain& D, double eta, cons
   if (!identity) f = D.lat_map[f];
   // the fine wall of cell (i, j): box_hit_in on the bounds just read
   const double sx = (xdn ? xlo : xhi) - px, sy = (ydn ? ylo : yhi) - py;
-  const double mx = __dmul_rn(fabs(sx), fabs(dx)), my = __dmul_rn(fabs(sy), fabs(dy));
-  const bool vx = (fabs(dx) >= 1e-10) & (mx > 0.0);
-  const bool vy = (fabs(dy) >= 1e-10) & (my > 0.0);
+  const bool vx = wall_candidate(sx, dx), vy = wall_candidate(sy, dy);
   const double cx = __dmul_rn(fabs(sx), fabs(dy)), cy = __dmul_rn(fabs(sy), fabs(dx));
   const bool xw = vx & (!vy | (y_first & (cx < cy)) | (!y_first & !(cy < cx)));
   const int wl = xw ? (xdn ? 3 : 1) : (ydn ? 0 : 2);

@@ -117,5 +117,11 @@ hipError_t launch_scan(const uint32_t* row_nnz, const uint32_t* row_tallied, int
                        int64_t* row_off, int64_t* totals, hipStream_t stream);
 hipError_t launch_pack(const uint32_t* stage_cols, const uint32_t* stage_cnt, int64_t row_cap, const int64_t* row_off,
                        int64_t n_rows, uint32_t* cols, uint32_t* cnt, hipStream_t stream);
+// Debug (rthx_debug_sin_theta_sweep, rthx_debug_sin_theta): sin_theta_u32 on
+// the words w_begin .. w_begin + n - 1 (n <= 2^32 - w_begin) against the
+// earlier expression, out[0] += differing words, out[1] = min(out[1], least
+// differing word); and sin_theta_u32 of given words.
+hipError_t launch_sin_theta_sweep(uint32_t w_begin, uint64_t n, unsigned long long* out, hipStream_t stream);
+hipError_t launch_sin_theta(const uint32_t* words, int64_t n, double* out, hipStream_t stream);
 
 }  // namespace rthx

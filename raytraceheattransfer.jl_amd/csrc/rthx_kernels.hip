@@ -1529,4 +1529,50 @@ hipError_t launch_pack(const uint32_t* stage_cols, const uint32_t* stage_cnt, in
   return hipGetLastError();
 }
 
+// Debug kernels of the theta draw's sine (rthx_debug_sin_theta_sweep,
+// rthx_debug_sin_theta): sin_theta_u32 against the earlier expression
+// 2.0 * sqrt_unit(u (1 - u)) on the words w_begin .. w_begin + n - 1, sixteen
+// words a lane.  out[0] += words whose bits differ, out[1] = min(out[1], the
+// least such word).
+constexpr int kSinThetaPerLane = 16;
+__global__ __launch_bounds__(256) void sin_theta_sweep_kernel(uint32_t w_begin, uint64_t n,
+                                                              unsigned long long* __restrict__ out) {
+  const uint64_t first = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * kSinThetaPerLane;
+  uint32_t n_diff = 0;
+  unsigned long long least = ~0ull;
+  for (int k = 0; k < kSinThetaPerLane; ++k) {
+    const uint64_t idx = first + k;
+    if (idx >= n) break;
+    const uint32_t w = w_begin + (uint32_t)idx;  // (the host checks w_begin + n <= 2^32)
+    if (dbits(sin_theta_u32(w)) != dbits(sin_theta_parent(w))) {
+      ++n_diff;
+      least = least < w ? least : (unsigned long long)w;
+    }
+  }
+  if (n_diff) {
+    atomicAdd(out, (unsigned long long)n_diff);
+    atomicMin(out + 1, least);
+  }
+}
+
+__global__ __launch_bounds__(256) void sin_theta_kernel(const uint32_t* __restrict__ words, int64_t n,
+                                                        double* __restrict__ out) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k < n) out[k] = sin_theta_u32(words[k]);
+}
+
+hipError_t launch_sin_theta_sweep(uint32_t w_begin, uint64_t n, unsigned long long* out, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  const uint64_t per_block = 256ull * kSinThetaPerLane;
+  hipLaunchKernelGGL(sin_theta_sweep_kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0, stream,
+                     w_begin, n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_sin_theta(const uint32_t* words, int64_t n, double* out, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(sin_theta_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, words, n, out);
+  return hipGetLastError();
+}
+
 }  // namespace rthx

@@ -123,6 +123,11 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib.rthx_trace_direct.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_uint8), C.POINTER(abi.DirectArgs),
                                       C.POINTER(C.c_uint64), C.POINTER(abi.DirectInfo)]
     lib.rthx_debug_alias.argtypes = [dp, C.c_int64, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "rthx_debug_wall_candidate"):  # (older A/B variant libraries lack these three)
+        lib.rthx_debug_wall_candidate.argtypes = [C.c_double, C.c_double, C.c_int32]
+        lib.rthx_debug_sin_theta_sweep.argtypes = [C.c_int32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64),
+                                                   C.POINTER(C.c_uint64)]
+        lib.rthx_debug_sin_theta.argtypes = [C.c_int32, C.POINTER(C.c_uint32), C.c_int64, dp]
     lib.rthx_scene3d_create.argtypes = [dp, C.POINTER(C.c_int32), dp, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
     if hasattr(lib, "rthx_scene3d_create_grouped"):  # (older A/B variant libraries lack it)
         lib.rthx_scene3d_create_grouped.argtypes = [dp, C.POINTER(C.c_int32), dp, C.POINTER(C.c_int32), C.c_int64,
