@@ -190,6 +190,28 @@ int rthx_domain_create(const rthx_domain_desc* desc, int32_t device,
                        rthx_domain** out);
 void rthx_domain_destroy(rthx_domain* dom);
 
+/* Specular symmetry walls.  mirror[n_coarse*4] (uint8, wall w of coarse polygon c at 4c + w, padded like
+ * coarse_solid); nonzero = a ray that reaches this wall is reflected about the wall's normal and goes on with
+ * the free path (optical depth) it has left; it is never tallied there, never crosses it and is not lost
+ * there.  NULL or all zero: no mirrors (the domain traces exactly as before the call).  A flagged wall that is
+ * solid, or a flag at w >= coarse_nv[c]: RTHX_EINVAL, and the domain keeps its previous setting.
+ * May be called any time between traces (one in-flight call per domain).
+ *  - The flag wins over a neighbour: a flagged wall between two coarse polygons reflects from both sides (the
+ *    neighbour's wall with the same two end points is flagged with it, unless that one is solid).
+ *  - Mirror walls are not surfaces: they own no row or column of the result.
+ *  - A ray still travelling after the walk's step cap (the 10,000 segments of traceRay.jl:27; a reflection
+ *    counts as a segment) is lost as without mirrors -- two facing mirrors in a transparent medium, for
+ *    example.  lost_total / lost_max_row count only such rays and rays that leave through an open wall.
+ *  - rthx_trace_exchange and rthx_trace_exchange_rays support mirrors with every emitter range, flag, copy,
+ *    accumulate and downstream call, bit-reproducibly.  With RTHX_FLAG_ASYNC the call blocks (a mirror domain
+ *    has no enqueue-only path).  A recorder (n_record > 0) and rthx_trace_direct on a domain with at least
+ *    one mirror are RTHX_EINVAL; rthx_multi has no mirror setter.
+ *  - A domain with a mirror is traced by the general polygon walker, not by the lattice or LDS-staged fast
+ *    paths its shape would otherwise select: expect a several times lower ray rate. */
+int rthx_domain_set_mirror_walls(rthx_domain* dom, const uint8_t* mirror);
+/* *n_mirror = number of flagged walls (0 for a domain never set). */
+int rthx_domain_get_mirror_walls(const rthx_domain* dom, int64_t* n_mirror);
+
 /* Result objects are reusable: tracing into an existing result reuses its
  * device buffers when they are large enough. */
 int rthx_result_create(rthx_result** out);

@@ -11,11 +11,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -449,6 +451,14 @@ RTHX_EXPORT int rthx_domain_create(const rthx_domain_desc* desc, int32_t device,
   }
   UP(cpoly.data(), nc, D.c_poly);
   UP(csolid.data(), nc, D.c_solid);
+  {  // no mirror walls until rthx_domain_set_mirror_walls flags some
+    const std::vector<uint32_t> none(nc, 0u);
+    UP(none.data(), nc, D.c_mirror);
+    d->d_mirror = const_cast<uint32_t*>(static_cast<const uint32_t*>(D.c_mirror));
+    d->c_nv.assign(s.coarse_nv, s.coarse_nv + nc);
+    d->c_xy.assign(s.coarse_xy, s.coarse_xy + 8 * nc);
+    d->c_solid = csolid;
+  }
   UP(s.coarse_bbox, 4 * nc, D.c_bbox);
   UP(s.fine_offset, nc + 1, D.f_offset);
   UP(s.fine_nv, nf, D.f_nv);
@@ -693,6 +703,57 @@ RTHX_EXPORT int rthx_domain_create(const rthx_domain_desc* desc, int32_t device,
   return RTHX_OK;
 }
 
+RTHX_EXPORT int rthx_domain_set_mirror_walls(rthx_domain* dom, const uint8_t* mirror) {
+  if (!dom) return fail(RTHX_EINVAL, "null domain");
+  const size_t nc = dom->c_nv.size();
+  std::vector<uint32_t> mask(nc, 0u);
+  int64_t n = 0;
+  for (size_t c = 0; mirror && c < nc; ++c)
+    for (int w = 0; w < 4; ++w) {
+      if (!mirror[4 * c + w]) continue;
+      if (w >= dom->c_nv[c]) return fail(RTHX_EINVAL, "mirror flag on a wall the coarse polygon does not have");
+      if ((dom->c_solid[c] >> w) & 1u) return fail(RTHX_EINVAL, "mirror flag on a solid wall");
+      mask[c] |= 1u << w;
+      ++n;
+    }
+  // A flagged wall between two coarse polygons reflects from both sides: the
+  // neighbour's wall with the same two end points takes the flag too (unless
+  // it is solid, where the ray ends anyway).
+  if (n > 0 && nc > 1) {
+    typedef std::array<double, 4> Key;  // the wall's end points, the smaller first
+    auto key_of = [&](size_t c, int w) {
+      const double* v = dom->c_xy.data() + 8 * c;
+      const int w2 = (w + 1) % dom->c_nv[c];
+      const std::pair<double, double> a{v[2 * w], v[2 * w + 1]}, b{v[2 * w2], v[2 * w2 + 1]};
+      return a < b ? Key{a.first, a.second, b.first, b.second} : Key{b.first, b.second, a.first, a.second};
+    };
+    std::map<Key, std::vector<std::pair<size_t, int>>> walls;
+    for (size_t c = 0; c < nc; ++c)
+      for (int w = 0; w < dom->c_nv[c]; ++w) walls[key_of(c, w)].push_back({c, w});
+    const std::vector<uint32_t> flagged = mask;
+    for (size_t c = 0; c < nc; ++c)
+      for (int w = 0; w < dom->c_nv[c]; ++w)
+        if ((flagged[c] >> w) & 1u)
+          for (const auto& o : walls[key_of(c, w)])
+            if (!((dom->c_solid[o.first] >> o.second) & 1u)) mask[o.first] |= 1u << o.second;
+  }
+  rthx::DeviceGuard keep_device;
+  HIP_TRY(hipSetDevice(dom->device), "hipSetDevice");
+  // (stream order: after every trace enqueued on this domain; the masks are
+  // in place when the call returns)
+  HIP_TRY(hipMemcpyAsync(dom->d_mirror, mask.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, dom->stream),
+          "hipMemcpy mirror masks");
+  HIP_TRY(hipStreamSynchronize(dom->stream), "mirror masks");
+  dom->n_mirror = n;
+  return RTHX_OK;
+}
+
+RTHX_EXPORT int rthx_domain_get_mirror_walls(const rthx_domain* dom, int64_t* n_mirror) {
+  if (!dom || !n_mirror) return fail(RTHX_EINVAL, "null domain or output");
+  *n_mirror = dom->n_mirror;
+  return RTHX_OK;
+}
+
 RTHX_EXPORT void rthx_domain_destroy(rthx_domain* dom) {
   if (!dom) return;
   (void)hipSetDevice(dom->device);
@@ -771,6 +832,14 @@ int plan_trace(const rthx_domain* dom, const rthx_trace_args* a, TracePlan& p, i
   if (a->emitter_stride < 1 || a->emitter_begin < 0) return fail(RTHX_EINVAL, "bad emitter range");
   if (!std::isfinite(a->nudge)) return fail(RTHX_EINVAL, "non-finite nudge");
   if (a->n_record < 0 || (a->n_record > 0 && !a->record_ids)) return fail(RTHX_EINVAL, "bad record ids");
+  // Mirror walls (rthx_domain_set_mirror_walls): the reflection lives in the
+  // general multi-polygon walker only, so such a domain is planned as a
+  // multi-polygon one without anything staged in LDS -- no lattice (LAT,
+  // MLAT, walk_layers), no coarse mesh in LDS, no look-back -- and no
+  // recording instance carries it.
+  p.mirror = dom->n_mirror > 0;
+  if (p.mirror && a->n_record > 0) return fail(RTHX_EINVAL, "ray recording is not supported on a domain with mirror walls");
+  const bool single = dom->single_convex && !p.mirror;
   p.N = dom->n_emitters;
   p.R = a->rays_per_emitter;
   p.end = std::min<int64_t>(a->emitter_end, p.N);
@@ -824,7 +893,7 @@ int plan_trace(const rthx_domain* dom, const rthx_trace_args* a, TracePlan& p, i
     // ascending output through an N-bit bitmap behind the table when it fits
     // (and leaves room for the single rectangle's lattice); else LDS sort
     const int64_t bm = (N + 31) / 32;
-    const size_t lat = dom->single_convex ? (size_t)dom->D.lat.bytes + 16 : 0;
+    const size_t lat = single ? (size_t)dom->D.lat.bytes + 16 : 0;
     if (p.lds_bytes + 4 * bm + lat + rthx::kStaticLdsBytes <= rthx::kMaxLdsBytes && !env_flag("RTHX_HASH_SORT")) {
       p.bm_words = bm;
       p.lds_bytes += 4 * (size_t)bm;
@@ -840,18 +909,18 @@ int plan_trace(const rthx_domain* dom, const rthx_trace_args* a, TracePlan& p, i
   p.cl_offset = (p.lds_bytes + 15) & ~(size_t)15;
   const bool axis = dom->axis_rect && !env_flag("RTHX_NO_AXIS");
   const bool no_clds = env_flag("RTHX_NO_CLDS");  // (tests: the global-memory multi-polygon kernels)
-  if (!dom->single_convex && axis && dom->D.ml.bytes > 0 && !no_clds &&
+  if (!p.mirror && !dom->single_convex && axis && dom->D.ml.bytes > 0 && !no_clds &&
       p.cl_offset + (size_t)dom->D.ml.bytes + (size_t)rthx::kTraceThreads * rthx::kRaySlotBytes +
               rthx::kStaticLdsBytes <= rthx::kMaxLdsBytes) {
     p.clds = 2;  // multi-polygon lattice (MLAT kernels)
     p.lds_bytes = p.cl_offset + (size_t)dom->D.ml.bytes;
-  } else if (!dom->single_convex && dom->D.cl.bytes > 0 &&
+  } else if (!p.mirror && !dom->single_convex && dom->D.cl.bytes > 0 &&
              p.cl_offset + (size_t)dom->D.cl.bytes + rthx::kStaticLdsBytes <= rthx::kMaxLdsBytes && !no_clds) {
     p.clds = 1;
     p.lds_bytes = p.cl_offset + (size_t)dom->D.cl.bytes;
   }
   // single axis-aligned rectangles: the lattice behind the histogram (LAT kernels)
-  if (dom->single_convex && dom->D.lat.bytes > 0 && !p.recording &&
+  if (single && dom->D.lat.bytes > 0 && !p.recording &&
       p.cl_offset + (size_t)dom->D.lat.bytes + rthx::kStaticLdsBytes <= rthx::kMaxLdsBytes) {
     p.clds = 1;
     p.lds_bytes = p.cl_offset + (size_t)dom->D.lat.bytes;
@@ -871,9 +940,12 @@ rthx::LaunchCfg launch_of(const rthx_domain* dom, const rthx_trace_args* a, cons
   L.tally = p.tally;
   L.threads = (int)env_int("RTHX_TRACE_THREADS", 0, 0, rthx::kMaxTraceThreads);
   L.faithful = (a->flags & RTHX_FLAG_FAITHFUL_SAMPLING) != 0;
-  L.single = dom->single_convex;
+  // (p.mirror, not the domain's present setting: a pending async trace that
+  // is traced again keeps the kernels it was planned with)
+  L.mirror = p.mirror;
+  L.single = dom->single_convex && !p.mirror;
   L.clds = p.clds;
-  L.axis = dom->axis_rect && !env_flag("RTHX_NO_AXIS");
+  L.axis = dom->axis_rect && !p.mirror && !env_flag("RTHX_NO_AXIS");
   L.T.split = (int32_t)p.split;
   L.T.n_rows = p.n_rows;
   L.rec.n = p.recording ? 1 : 0;
@@ -1148,7 +1220,7 @@ int trace_exchange_one(rthx_domain* dom, const rthx_trace_args* a, rthx_result* 
   // layers), and a row waiting on a slower predecessor idles its CU slot
   // (C5 greenhouse: 15.2 -> 17.6 ms per band with the look-back).  The
   // recorder's kernels stage.
-  const bool lookback = !p.part_lists && n_rows > 0 && dom->single_convex && !p.recording &&
+  const bool lookback = !p.part_lists && n_rows > 0 && dom->single_convex && !p.mirror && !p.recording &&
                         (uint64_t)n_rows * (uint64_t)p.row_cap <= rthx::kLbValMax && !env_flag("RTHX_NO_LOOKBACK");
   // The replaced launch's stall / overflow flags: read by this launch's row 0
   // when it uses the same look-back totals without zeroing them (run_trace),

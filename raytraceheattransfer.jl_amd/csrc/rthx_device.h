@@ -170,6 +170,9 @@ struct DevDomain {
   const uint4 RTHX_GLOBAL* ml_blob;    // [ml.blob_bytes / 16]
   const double RTHX_GLOBAL* ml_bbeta;  // [n_bins][n_coarse] beta of box b (-1: per fine polygon)
   MLatLayout ml;
+  // specular symmetry walls (rthx_domain_set_mirror_walls; read by the MIRROR
+  // instances of segment() only).  Last, so that no other field moves.
+  const uint32_t RTHX_GLOBAL* c_mirror;  // [n_coarse] bit w = wall w reflects
 };
 
 struct TraceParams {
@@ -1028,9 +1031,20 @@ constexpr int kRayContinue = -3;  // segment(): the ray crossed into another coa
 // lost ray, or kRayContinue after a crossing (p, c, S / acc updated).
 // UNIFORM: S is the free path left; otherwise S is tau* and acc the optical
 // depth accumulated so far.
-template <bool UNIFORM, bool SINGLE, bool AXIS>
+// MIRROR (multi-polygon instances): a ray that reaches a wall
+// flagged in D.c_mirror[c] -- neither absorbed on the way nor at a solid wall --
+// stops eta short of it, as at a solid wall, so that it stays in polygon c;
+// its direction is reflected about the wall's normal, d <- d - 2 (d.n) n (an
+// exact sign flip for an axis-aligned wall: the products with 0 and +-1 are
+// exact; the stored normal's orientation does not matter), the segment is
+// charged to the free path as a crossing charges it, and the walk goes on in
+// c (kRayContinue: a reflection counts towards the caller's step cap).  The
+// flag wins over a neighbour behind the wall.  A polygon without a wall ahead
+// (u = +inf) reflects nothing.  Without MIRROR d is never written.
+template <bool UNIFORM, bool SINGLE, bool AXIS, bool MIRROR = false>
 __device__ __forceinline__ int segment(const DevDomain& D, const TraceParams& P, const SingleCoarse& sc, int& c,
-                                       double& px, double& py, double dx, double dy, double& S, double& acc) {
+                                       double& px, double& py, double& dx, double& dy, double& S, double& acc) {
+  static_assert(!(MIRROR && SINGLE), "mirror domains take the multi-polygon walker");
   const double eta = P.eta;
   int k, first, count;
   double u;
@@ -1071,6 +1085,20 @@ __device__ __forceinline__ int segment(const DevDomain& D, const TraceParams& P,
     return D.f_surf[4 * fg + w];  // -1 if the fine wall is not solid
   }
   if (SINGLE) return -1;  // an open wall of the only polygon leads outside: locate_coarse finds nothing
+  if constexpr (MIRROR) {
+    if (((D.c_mirror[c] >> k) & 1u) && u < __builtin_inf()) {
+      const double t = u - eta;
+      px = px + __dmul_rn(t, dx);
+      py = py + __dmul_rn(t, dy);
+      const DevPoly RTHX_GLOBAL& q = D.c_poly[c];
+      const double nx = q.nx[k], ny = q.ny[k];
+      const double dn2 = 2.0 * (__dmul_rn(dx, nx) + __dmul_rn(dy, ny));
+      dx = dx - __dmul_rn(dn2, nx);
+      dy = dy - __dmul_rn(dn2, ny);
+      if (UNIFORM) S -= u; else acc += tau_b;
+      return kRayContinue;
+    }
+  }
   double t = u + eta;
   px = px + __dmul_rn(t, dx);
   py = py + __dmul_rn(t, dy);

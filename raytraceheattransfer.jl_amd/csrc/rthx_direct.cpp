@@ -107,6 +107,7 @@ RTHX_EXPORT int rthx_trace_direct(rthx_domain* dom, const double* weights, const
                                   rthx_direct_info* info) {
   const double t0 = now_ms();
   if (!dom || !a || !counts || !weights || !omega || !reemit) return fail(RTHX_EINVAL, "null argument");
+  if (dom->n_mirror > 0) return fail(RTHX_EINVAL, "the direct method is not supported on a domain with mirror walls");
   const rthx::DevDomain& D = dom->D;
   const int64_t n = dom->n_emitters;
   const int32_t ns = D.n_surfaces;

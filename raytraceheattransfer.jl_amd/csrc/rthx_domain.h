@@ -26,6 +26,7 @@ struct TracePlan {
   int tally = 1;            // rthx_kernels.h Tally (kTallyU16)
   int clds = 0;             // rthx_kernels.h LaunchCfg::clds
   bool recording = false, uniform = true;
+  bool mirror = false;      // the domain had mirror walls when the trace was planned (LaunchCfg::mirror)
   size_t lds_bytes = 0, cl_offset = 0;
 };
 struct DirectWork;                   // rthx_direct.cpp: device buffers of rthx_trace_direct
@@ -46,6 +47,15 @@ struct rthx_domain {
   bool single_convex = false;        // one convex coarse polygon (SINGLE kernels)
   bool axis_rect = false;            // every polygon an axis-aligned rectangle in canonical order (AXIS kernels)
   std::vector<uint8_t> ml_mixed;     // MLAT: per bin, 1 if some coarse box has no single beta (TraceParams::mixed)
+  // rthx_domain_set_mirror_walls: the coarse polygons' vertex counts, vertices
+  // and solid masks (the setter's checks and its search for a flagged wall's
+  // neighbour), the device masks D.c_mirror points to (zero from
+  // rthx_domain_create on) and the number of walls the caller flagged
+  std::vector<int32_t> c_nv;
+  std::vector<double> c_xy;  // [n_coarse][4][2]
+  std::vector<uint32_t> c_solid;
+  uint32_t* d_mirror = nullptr;
+  int64_t n_mirror = 0;
   rthx::DirectWork* direct = nullptr;  // created by the first rthx_trace_direct call
   ~rthx_domain() {
     if (direct) rthx::destroy_direct_work(direct);

@@ -100,6 +100,7 @@ struct LaunchCfg {
   int threads;  // workgroup size; 0 = the one with the most resident waves
   int clds;  // LDS behind the tally: 0 none, 1 coarse mesh (multi-polygon) or LAT (single), 2 MLAT
   bool uniform, faithful, single, axis;
+  bool mirror = false;  // the domain has mirror walls: the MIRROR instances (single, axis, clds and rec.n are then 0)
   // Set: nothing is launched; *slots gets the workgroups of this launch's
   // kernel and workgroup size that are resident at once on the device (CUs x
   // workgroups per CU), so the host can size a row split to one round.

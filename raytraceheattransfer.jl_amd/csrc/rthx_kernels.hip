@@ -423,10 +423,15 @@ __device__ __forceinline__ uint32_t hash_emit_bitmap(const uint32_t* keys, const
   return total;
 }
 
-template <bool UNIFORM, int TALLY, bool FAITHFUL, bool SINGLE, bool REC, bool SPLIT, bool AXIS, int CL, bool RBASE>
+// MIRROR: the domain has specular symmetry walls (DevDomain::c_mirror): the
+// ray-regeneration loop's segment() reflects at them.  Only the general
+// multi-polygon instances exist with it (!SINGLE, !AXIS, CL = 0, !REC).
+template <bool UNIFORM, int TALLY, bool FAITHFUL, bool SINGLE, bool REC, bool SPLIT, bool AXIS, int CL, bool RBASE,
+          bool MIRROR = false>
 __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_exchange_kernel(const DevDomain* __restrict__ Dp,
                                                                      TraceParams P, TallyParams T,
                                                                      RecordParams rec) {
+  static_assert(!MIRROR || (!SINGLE && !AXIS && CL == 0 && !REC), "mirror walls: the general multi-polygon walker only");
   extern __shared__ __attribute__((aligned(16))) uint32_t hist[];  // (zeroed and handed off as uint4s)
   const DevDomain& D = *Dp;
   __shared__ uint32_t wave_sum[kMaxTraceThreads / 64];
@@ -886,7 +891,7 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
             const CoarseLds L = coarse_lds_view(lds_opaque(cl_base), D.cl);
             a = walk_cl<UNIFORM, AXIS>(D, P, L, c, px, py, dx, dy, S, acc);
           } else {
-            a = segment<UNIFORM, false, AXIS>(D, P, s_single, c, px, py, dx, dy, S, acc);
+            a = segment<UNIFORM, false, AXIS, MIRROR>(D, P, s_single, c, px, py, dx, dy, S, acc);
           }
         }
         ++it;
@@ -1365,13 +1370,13 @@ static int device_cus() {
 }
 
 template <bool UNIFORM, int TALLY, bool FAITHFUL, bool SINGLE, bool REC, bool SPLIT, bool AXIS, int CL = 0,
-          bool RBASE = false>
+          bool RBASE = false, bool MIRROR = false>
 static hipError_t launch_trace_t(const LaunchCfg& L) {
   // SINGLE kernels: a ray base that is not 0 runs the RBASE instance (the
   // others read TraceParams::ray_base as it is)
   if constexpr (SINGLE && !RBASE)
     if (L.P.ray_base != 0) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, SINGLE, REC, SPLIT, AXIS, CL, true>(L);
-  auto kern = trace_exchange_kernel<UNIFORM, TALLY, FAITHFUL, SINGLE, REC, SPLIT, AXIS, CL, RBASE>;
+  auto kern = trace_exchange_kernel<UNIFORM, TALLY, FAITHFUL, SINGLE, REC, SPLIT, AXIS, CL, RBASE, MIRROR>;
   const int64_t blocks = L.T.n_rows * (SPLIT ? L.T.split : 1);
   // (MLAT kernels: a 64-slot ray queue per wave behind the lattice)
   auto lds_for = [&](int t) { return L.lds_bytes + (CL == 2 && !SINGLE ? (size_t)t * kRaySlotBytes : 0); };
@@ -1454,6 +1459,13 @@ static hipError_t launch_trace_a(const LaunchCfg& L) {
 
 template <bool UNIFORM, int TALLY, bool FAITHFUL>
 static hipError_t launch_trace_u(const LaunchCfg& L) {
+  // Mirror walls: the general multi-polygon walker with the reflection in
+  // segment(), whatever the domain's shape (no SINGLE, AXIS, LDS-staged or
+  // recording instance carries it; the host plans none of them for a domain
+  // with a mirror).
+  if (L.mirror)
+    return L.T.split > 1 ? launch_trace_t<UNIFORM, TALLY, FAITHFUL, false, false, true, false, 0, false, true>(L)
+                         : launch_trace_t<UNIFORM, TALLY, FAITHFUL, false, false, false, false, 0, false, true>(L);
   // Recording is a plotting aid: generic (non-SINGLE, general polygon)
   // instances carry it, unsplit -- or split into hash-tallied parts when a
   // large-N row holds more rays than one table (the recorder writes ray r of

@@ -54,6 +54,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib.rthx_domain_create.argtypes = [C.POINTER(abi.DomainDesc), C.c_int32, C.POINTER(C.c_void_p)]
     lib.rthx_domain_destroy.argtypes = [C.c_void_p]
     lib.rthx_domain_destroy.restype = None
+    lib.rthx_domain_set_mirror_walls.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
+    lib.rthx_domain_get_mirror_walls.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     lib.rthx_result_create.argtypes = [C.POINTER(C.c_void_p)]
     lib.rthx_result_destroy.argtypes = [C.c_void_p]
     lib.rthx_result_destroy.restype = None
@@ -246,6 +248,31 @@ class DeviceDomain:
         h = C.c_void_p()
         check(self._lib.rthx_domain_create(C.byref(flat.desc), device, C.byref(h)))
         self.handle = h
+        self.n_coarse = flat.n_coarse
+        mirror = getattr(flat, "coarse_mirror", None)
+        if mirror is not None and mirror.any():
+            try:
+                self.set_mirror_walls(mirror)
+            except Exception:
+                self.close()
+                raise
+
+    def set_mirror_walls(self, mirror) -> None:
+        """rthx_domain_set_mirror_walls: ``mirror`` is uint8 [n_coarse, 4]
+        (nonzero = specular symmetry wall) or None for no mirrors."""
+        if mirror is None:
+            check(self._lib.rthx_domain_set_mirror_walls(self.handle, C.cast(None, C.POINTER(C.c_uint8))))
+            return
+        m = np.ascontiguousarray(np.asarray(mirror, dtype=np.uint8).reshape(-1))
+        if m.size != 4 * self.n_coarse:
+            raise ValueError("mirror must hold 4 flags per coarse polygon")
+        check(self._lib.rthx_domain_set_mirror_walls(self.handle, abi.ptr(m, C.c_uint8)))
+
+    def mirror_walls(self) -> int:
+        """Number of flagged mirror walls (rthx_domain_get_mirror_walls)."""
+        n = C.c_int64(0)
+        check(self._lib.rthx_domain_get_mirror_walls(self.handle, C.byref(n)))
+        return n.value
 
     def close(self) -> None:
         if getattr(self, "handle", None):
@@ -265,6 +292,9 @@ class MultiDeviceDomain:
 
     def __init__(self, flat, devices: Sequence[int]):
         self._lib = load()
+        mirror = getattr(flat, "coarse_mirror", None)
+        if mirror is not None and mirror.any():
+            raise RthxError("mirror walls are not supported on several devices (rthx_multi has no mirror setter)")
         self.devices = [int(d) for d in devices]
         self.n_emitters = flat.n_emitters
         devs = (C.c_int32 * len(self.devices))(*self.devices)

@@ -291,6 +291,8 @@ EXPORTED_SYMBOLS = (
     "rthx_device_synchronize",
     "rthx_domain_create",
     "rthx_domain_destroy",
+    "rthx_domain_set_mirror_walls",
+    "rthx_domain_get_mirror_walls",
     "rthx_result_create",
     "rthx_result_destroy",
     "rthx_trace_exchange",

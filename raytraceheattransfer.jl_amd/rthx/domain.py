@@ -178,6 +178,10 @@ class FlatDomain:
             cs[k, : f.n] = f.solidWalls
         self.coarse_normal = np.ascontiguousarray(cn.reshape(-1))
         self.coarse_solid = np.ascontiguousarray(cs.reshape(-1))
+        # specular symmetry walls (rthx_domain_set_mirror_walls): uint8 [n_coarse, 4], padded like coarse_solid
+        self.coarse_mirror = np.zeros((self.n_coarse, 4), dtype=np.uint8)
+        for k, f in enumerate(coarse):
+            self.coarse_mirror[k, : f.n] = getattr(f, "mirrorWalls", [False] * f.n)
         self.coarse_bbox = np.ascontiguousarray(dom.coarse_bboxes.reshape(-1))
 
         self.fine_offset = np.zeros(self.n_coarse + 1, dtype=np.int32)

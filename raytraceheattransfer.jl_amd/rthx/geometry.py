@@ -55,10 +55,17 @@ class PolyVolume2D:
     Mirrors ``PolyVolume2D{Float64}(vertices, solidWalls, n_spectral_bins,
     kappa, sigma_s)`` (PolyVolume2D.jl:2-4, :96-98).  Grey faces hold scalar
     ``kappa_g`` / ``sigma_s_g``; spectral faces hold length-``n_bins`` arrays.
+
+    ``mirror_walls`` (not in the reference): one bool per wall, true for a
+    specular symmetry wall -- a non-solid wall that reflects the ray, so that
+    half or a quarter of a symmetric enclosure can be modelled (DESIGN.md
+    §7j).  The flag lives on the coarse polygon only: sub-volumes do not
+    inherit it, and a mirror wall is no surface.
     """
 
     def __init__(self, vertices: Sequence[Tuple[Number, Number]], solid_walls: Sequence[bool],
-                 n_spectral_bins: int = 1, kappa: Spectral = 0.0, sigma_s: Spectral = 0.0):
+                 n_spectral_bins: int = 1, kappa: Spectral = 0.0, sigma_s: Spectral = 0.0,
+                 mirror_walls: Sequence[bool] = None):
         n = len(vertices)
         if n not in (3, 4):
             raise ValueError("Only triangles and quadrilaterals are supported.")
@@ -66,6 +73,13 @@ class PolyVolume2D:
             raise ValueError("solid_walls must have one entry per wall")
         self.vertices = [(float(x), float(y)) for x, y in vertices]
         self.solidWalls = [bool(b) for b in solid_walls]
+        if mirror_walls is None:
+            mirror_walls = [False] * n
+        if len(mirror_walls) != n:
+            raise ValueError("mirror_walls must have one entry per wall")
+        self.mirrorWalls = [bool(b) for b in mirror_walls]
+        if any(s and m for s, m in zip(self.solidWalls, self.mirrorWalls)):
+            raise ValueError("a wall cannot be both solid and a mirror")
         v = self.vertices
         if n == 4:
             self.midPoint = ((v[0][0] + v[1][0] + v[2][0] + v[3][0]) / 4,
