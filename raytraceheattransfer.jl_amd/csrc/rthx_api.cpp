@@ -230,6 +230,24 @@ extern "C" __attribute__((visibility("default"))) int rthx_debug_wall_candidate(
   }
 }
 
+// Host evaluation of the LAT ray's choice of the x wall in the coarse
+// two-wall test (rthx_device.h): form 0 the deferred copy's x_wall_untied,
+// bit 0 the choice and bit 1 its tie flag; form 1 the reference form with the
+// tie order y_first, bit 0.  cx, cy: the cross products |sx||dy|, |sy||dx|.
+extern "C" __attribute__((visibility("default"))) int rthx_debug_x_wall(int32_t vx, int32_t vy, int32_t y_first,
+                                                                        double cx, double cy, int32_t form) {
+  const bool bx = vx != 0, by = vy != 0, yf = y_first != 0;
+  switch (form) {
+    case 0: {
+      bool tie = false;
+      const bool xw = rthx::x_wall_untied(bx, by, cx, cy, tie);
+      return (xw ? 1 : 0) | (tie ? 2 : 0);
+    }
+    case 1: return (bx & (!by | (yf & (cx < cy)) | (!yf & !(cy < cx)))) ? 1 : 0;
+    default: return -1;
+  }
+}
+
 // The theta draw's sine on the device (sin_theta_u32, rthx_device.h), for
 // tests.  The sweep compares it with the earlier expression
 // 2.0 * sqrt_unit(u (1 - u)) on the n words from w_begin (w_begin + n <= 2^32)
@@ -748,6 +766,16 @@ RTHX_EXPORT int rthx_domain_set_mirror_walls(rthx_domain* dom, const uint8_t* mi
   return RTHX_OK;
 }
 
+// Whether the domain's LAT rows take the closed-enclosure copy of the LAT ray
+// (lat_plain, rthx_device.h, on the host's copy of the domain record): 1 or
+// 0, -1 for a domain without the lattice.  The launcher's own choice of the
+// PLAINK instances (launch_of) and the tests' view of it; not part of
+// include/rthx.h.
+extern "C" __attribute__((visibility("default"))) int rthx_debug_lat_plain(const rthx_domain* dom) {
+  if (!dom || dom->D.lat.bytes <= 0 || dom->c_solid.empty()) return -1;
+  return rthx::lat_plain(dom->c_solid[0], dom->D.lat.identity) ? 1 : 0;
+}
+
 RTHX_EXPORT int rthx_domain_get_mirror_walls(const rthx_domain* dom, int64_t* n_mirror) {
   if (!dom || !n_mirror) return fail(RTHX_EINVAL, "null domain or output");
   *n_mirror = dom->n_mirror;
@@ -943,6 +971,7 @@ rthx::LaunchCfg launch_of(const rthx_domain* dom, const rthx_trace_args* a, cons
   // (p.mirror, not the domain's present setting: a pending async trace that
   // is traced again keeps the kernels it was planned with)
   L.mirror = p.mirror;
+  L.lat_plain = rthx_debug_lat_plain(dom) == 1;
   L.single = dom->single_convex && !p.mirror;
   L.clds = p.clds;
   L.axis = dom->axis_rect && !p.mirror && !env_flag("RTHX_NO_AXIS");

@@ -376,6 +376,10 @@ __host__ __device__ __forceinline__ double neg_log_tab(double u, const double* t
 // u's plus 32 in the exponent field, so the table index and z are the same
 // and only k moves by 32 (an integer subtract instead of v_ldexp_f64).
 // Bit-identical to neg_log_tab(u32(w)) for every w (w = 0 -> +inf).
+// RAW: without the select for w = 0 (some finite or non-finite value there;
+// the table offset is masked, so the loads stay in range): for a caller that
+// handles w = 0 itself (the LAT ray's deferred copy, lat_ray_fast).
+template <bool RAW = false>
 __host__ __device__ __forceinline__ double neg_log_u32(uint32_t w, const double* tab) {
   // The low word of kLogOff and of the exponent mask is zero, so tmp's low
   // word is ix's and every step below is neg_log_tab's on the high word
@@ -401,6 +405,7 @@ __host__ __device__ __forceinline__ double neg_log_u32(uint32_t w, const double*
   const double hi = __builtin_fma(-kd, 6.93147180369123816490e-01, t_hi);
   const double lo = __builtin_fma(-kd, 1.90821492927058770002e-10, t_lo) - l1p;
   const double v = hi + lo;
+  if (RAW) return v;
   return w != 0u ? v : __builtin_inf();
 }
 
@@ -1297,28 +1302,58 @@ __device__ __forceinline__ int lattice_guess(double x, double x0, double inv, in
   return i;
 }
 
+// The coarse two-wall test's choice of the x wall without the tie order: the
+// reference form vx & (!vy | (y_first & cx < cy) | (!y_first & !(cy < cx)))
+// reads y_first only where cx == cy, so off a tie it is vx & (!vy | cx < cy);
+// `tie` says that the value may differ from the reference form's (the caller
+// does not use it then).  rthx_debug_x_wall evaluates both on the host.
+__host__ __device__ __forceinline__ bool x_wall_untied(bool vx, bool vy, double cx, double cy, bool& tie) {
+  tie = cx == cy;
+  return vx & (!vy | (cx < cy));
+}
+
 // INSIDE: as segment_lat.  identity: LatticeLayout::identity (uniform).
 // Returns the absorber of a lane that is not cold.
-template <bool INSIDE>
+// PLAIN: the copy for a closed enclosure on a lattice in cell order
+// (lat_plain below).  All four coarse walls are solid, so a ray that the gas
+// does not absorb ends on a solid wall whichever wall it is: wall = !gas and
+// lost = false, the values the general copy computes there, and the coarse
+// wall index k, which only the solid bit reads, is not formed.  The lattice
+// is in cell order, so lat_map is not read either.  Everything else is the
+// general copy's, text for text.
+// DEFER: the copy whose cold lanes are traced again from their ray index
+// (trace_exchange_kernel), so nothing of a cold lane's result is used and
+// three rare conditions of the coarse test become terms of `cold` instead of
+// selects: no candidate wall (!any; u stays the quotient, not +inf), an
+// exact tie cx == cy of the cross products (the tie order y_first is not
+// applied) and the caller's cold1 (the free-path word is 0 and S was taken
+// without its select, start_ray_w's RAW).  Such a lane runs on with whatever
+// values it has; its loads stay in range (the clamped guesses, below).
+template <bool INSIDE, bool PLAIN = false, bool DEFER = false>
 __device__ __forceinline__ int lat_ray_fast(const DevDomain& D, double eta, const SingleCoarse& sc,
-                                            const char RTHX_LDS* lat_base, bool identity, bool cold0, LatRay& r) {
+                                            const char RTHX_LDS* lat_base, bool identity, bool cold0, LatRay& r,
+                                            bool cold1 = false) {
   const double ox = r.px, oy = r.py, dx = r.dx, dy = r.dy, S = r.S;
   const double cx0 = sc.poly.x[0], cx1 = sc.poly.x[1], cy0 = sc.poly.y[0], cy1 = sc.poly.y[2];
   const bool xdn = dx < 0.0, ydn = dy < 0.0;
   const bool y_first = ydn | xdn;
   double u;
   int k;
+  bool rare = false;  // (DEFER)
   if (INSIDE) {
     // dist_in_box / box_hit_in, the division unconditional
     const double xb = xdn ? cx0 : cx1, yb = ydn ? cy0 : cy1;
     const double sx = xb - ox, sy = yb - oy;
     const bool vx = wall_candidate(sx, dx), vy = wall_candidate(sy, dy);
     const double cx = __dmul_rn(fabs(sx), fabs(dy)), cy = __dmul_rn(fabs(sy), fabs(dx));
-    const bool xw = vx & (!vy | (y_first & (cx < cy)) | (!y_first & !(cy < cx)));
+    bool tie = false;
+    const bool xw = DEFER ? x_wall_untied(vx, vy, cx, cy, tie)
+                          : vx & (!vy | (y_first & (cx < cy)) | (!y_first & !(cy < cx)));
     const bool any = vx | vy;
     const double q = div_pos(fabs(xw ? sx : sy), fabs(xw ? dx : dy));
-    u = any ? q : __builtin_inf();
-    k = any ? (xw ? (xdn ? 3 : 1) : (ydn ? 0 : 2)) : 0;
+    u = DEFER ? q : any ? q : __builtin_inf();
+    if (DEFER) rare = !any | tie;
+    k = PLAIN ? 0 : any ? (xw ? (xdn ? 3 : 1) : (ydn ? 0 : 2)) : 0;
   } else {
     // (a surface emitter's rays: segment_lat's choice of the test)
     if (cx0 <= ox && ox < cx1 && cy0 <= oy && oy < cy1)
@@ -1327,8 +1362,8 @@ __device__ __forceinline__ int lat_ray_fast(const DevDomain& D, double eta, cons
       u = dist_to_box(ox, oy, dx, dy, cx0, cx1, cy0, cy1, k);
   }
   const bool gas = S < u;
-  const bool wall = !gas & (((sc.solid >> k) & 1u) != 0u);
-  const bool lost = !(gas | wall);
+  const bool wall = PLAIN ? !gas : !gas & (((sc.solid >> k) & 1u) != 0u);
+  const bool lost = PLAIN ? false : !(gas | wall);
   const double t = (gas ? S : u) - eta;
   const double px = ox + __dmul_rn(t, dx);
   const double py = oy + __dmul_rn(t, dy);
@@ -1345,7 +1380,7 @@ __device__ __forceinline__ int lat_ray_fast(const DevDomain& D, double eta, cons
   const double xlo = xs[i], xhi = xs[i + 1], ylo = ys[j], yhi = ys[j + 1];
   const bool hit = (xlo <= px) & (px < xhi) & (ylo <= py) & (py < yhi);
   int f = lat_cell(i, j, G.nx);
-  if (!identity) f = D.lat_map[f];
+  if (!PLAIN && !identity) f = D.lat_map[f];
   // the fine wall of cell (i, j): box_hit_in on the bounds just read
   const double sx = (xdn ? xlo : xhi) - px, sy = (ydn ? ylo : yhi) - py;
   const bool vx = wall_candidate(sx, dx), vy = wall_candidate(sy, dy);
@@ -1359,7 +1394,17 @@ __device__ __forceinline__ int lat_ray_fast(const DevDomain& D, double eta, cons
   if (wall) surf = ld_off32(D.f_surf, ((uint32_t)f << 4) + ((uint32_t)wl << 2));
   const int a = gas ? sc.n_surfaces + f : surf;
   r.cold = cold0 | lost | !hit | (wall & !(vx | vy)) | (a < 0);
+  if (DEFER) r.cold |= cold1 | rare;
   return a;
+}
+
+// Whether a LAT domain's rows take lat_ray_fast's PLAIN copy: the coarse
+// rectangle's four walls solid (SingleCoarse::solid, bit w = wall w) and the
+// lattice in cell order.  The host evaluates it on its copy of the domain
+// record (rthx_debug_lat_plain) and launches the PLAINK instances of the
+// trace kernel for such a domain.
+__host__ __device__ __forceinline__ bool lat_plain(uint32_t solid, int identity) {
+  return (solid & 0xFu) == 0xFu && identity != 0;
 }
 
 // The cold lanes' continuation (see above): the absorber, -1 for a lost ray.
@@ -1936,11 +1981,12 @@ __device__ __forceinline__ double free_path(const TraceParams& P, const double* 
 // free_path(u32(w)), the table log taken from w directly (neg_log_u32).
 // LATRAY (the LAT ray, lat_ray_fast): 1 / beta comes from the coarse record
 // in LDS (the same value).
-template <bool UNIFORM, bool FAITHFUL, bool LATRAY = false>
+// RAW: neg_log_u32<true> (the caller handles w = 0).
+template <bool UNIFORM, bool FAITHFUL, bool LATRAY = false, bool RAW = false>
 __device__ __forceinline__ double free_path_u32(const TraceParams& P, const double* tabs, uint32_t w,
                                                 const SingleCoarse* sc = nullptr) {
   if (FAITHFUL) return free_path<UNIFORM, true>(P, tabs, u32(w));
-  const double l = neg_log_u32(w, tabs + kLogTableOffset);
+  const double l = neg_log_u32<RAW>(w, tabs + kLogTableOffset);
   if (UNIFORM) return l * (LATRAY ? sc->inv_beta : tabs[kTabInvBeta]);  // (P.inv_beta_uniform; l in (0, inf]: inf for beta_uniform <= 0)
   return l;
 }
@@ -1978,10 +2024,12 @@ __device__ __forceinline__ RayWords ray_words(const TraceParams& P, const Emitte
 }
 
 // Emission of ray (g, r): point, direction and free path / tau*.
-template <bool UNIFORM, bool FAITHFUL, int EK = kEmitAny, bool LATRAY = false>
+// w_zero (not null): the free-path word is 0, and S is then taken without the
+// select that makes it +inf (free_path_u32's RAW).
+template <bool UNIFORM, bool FAITHFUL, int EK = kEmitAny, bool LATRAY = false, bool RAW = false>
 __device__ __forceinline__ void start_ray_w(const TraceParams& P, const Emitter& e, const double* tabs,
                                             const RayWords& rw, double& px, double& py, double& dx, double& dy,
-                                            double& S, const SingleCoarse* sc = nullptr) {
+                                            double& S, const SingleCoarse* sc = nullptr, bool* w_zero = nullptr) {
   const bool surface = emitter_surface<EK>(e);
   if (surface)
     emit_surface<FAITHFUL>(e, P.eta, rw, tabs, px, py, dx, dy);
@@ -1991,7 +2039,13 @@ __device__ __forceinline__ void start_ray_w(const TraceParams& P, const Emitter&
   // dynamically indexed scratch load)
   uint32_t w_surf = rw.a[3], w_vol = rw.pw;
   __asm__ volatile("" : "+v"(w_surf), "+v"(w_vol));
-  S = free_path_u32<UNIFORM, FAITHFUL, LATRAY>(P, tabs, surface ? w_surf : w_vol, sc);
+  if constexpr (RAW) {
+    const uint32_t w = surface ? w_surf : w_vol;
+    S = free_path_u32<UNIFORM, FAITHFUL, LATRAY, true>(P, tabs, w, sc);
+    *w_zero = w == 0u;
+  } else {
+    S = free_path_u32<UNIFORM, FAITHFUL, LATRAY>(P, tabs, surface ? w_surf : w_vol, sc);
+  }
 }
 
 template <bool UNIFORM, bool FAITHFUL>

@@ -13,6 +13,9 @@ constexpr int kTraceThreads = 256;               // default workgroup: 4 waves o
 constexpr int kMaxTraceThreads = 1024;           // large-N rows (LDS-bound occupancy) use up to 16 waves
 constexpr size_t kMaxLdsBytes = 160 * 1024;      // gfx950 LDS per CU
 constexpr int64_t kStaticLdsBytes = 10240;      // bound on the trace kernel's static LDS (emitter, coarse polygon, ...)
+// cold rays a row of the LAT ray's closed-enclosure copy lists: 512 bytes of static LDS (and a counter) in the six
+// PLAINK instances of the trace kernel, which alone use them; no other instance allocates them
+constexpr int kLatColdList = 128;
 constexpr size_t kMaxCoarseLdsBytes = 48 * 1024; // largest coarse mesh the CLDS kernels stage in LDS
 
 struct RecordParams {
@@ -100,6 +103,9 @@ struct LaunchCfg {
   int threads;  // workgroup size; 0 = the one with the most resident waves
   int clds;  // LDS behind the tally: 0 none, 1 coarse mesh (multi-polygon) or LAT (single), 2 MLAT
   bool uniform, faithful, single, axis;
+  // LAT rows of a closed enclosure on a lattice in cell order (lat_plain on the host's domain record): the
+  // PLAINK instances, which hold the closed-enclosure copy of the LAT ray and nothing of the general one
+  bool lat_plain = false;
   bool mirror = false;  // the domain has mirror walls: the MIRROR instances (single, axis, clds and rec.n are then 0)
   // Set: nothing is launched; *slots gets the workgroups of this launch's
   // kernel and workgroup size that are resident at once on the device (CUs x

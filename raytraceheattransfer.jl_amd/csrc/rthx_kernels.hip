@@ -427,16 +427,23 @@ __device__ __forceinline__ uint32_t hash_emit_bitmap(const uint32_t* keys, const
 // ray-regeneration loop's segment() reflects at them.  Only the general
 // multi-polygon instances exist with it (!SINGLE, !AXIS, CL = 0, !REC).
 template <bool UNIFORM, int TALLY, bool FAITHFUL, bool SINGLE, bool REC, bool SPLIT, bool AXIS, int CL, bool RBASE,
-          bool MIRROR = false>
+          bool MIRROR = false, bool PLAINK = false>
 __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_exchange_kernel(const DevDomain* __restrict__ Dp,
                                                                      TraceParams P, TallyParams T,
                                                                      RecordParams rec) {
+  static_assert(!PLAINK || (SINGLE && CL != 0 && AXIS && UNIFORM && !RBASE && !FAITHFUL && !REC),
+                "the closed-enclosure copy: uniform LAT rows, ray base 0, no faithful sampling");
   static_assert(!MIRROR || (!SINGLE && !AXIS && CL == 0 && !REC), "mirror walls: the general multi-polygon walker only");
   extern __shared__ __attribute__((aligned(16))) uint32_t hist[];  // (zeroed and handed off as uint4s)
   const DevDomain& D = *Dp;
   __shared__ uint32_t wave_sum[kMaxTraceThreads / 64];
   __shared__ uint32_t s_tallied;
   __shared__ uint32_t s_next;  // next ray index of the row (ray regeneration, multi-polygon domains)
+  // The LAT ray's closed-enclosure copy: the row's (or part's) cold rays, by
+  // ray index, traced after the round loop; s_cold_n counts past the list's
+  // end (then the whole row is traced again).  Used by those instances alone.
+  __shared__ uint32_t s_cold_n;
+  __shared__ uint32_t s_cold[kLatColdList];
   // Emitter data is workgroup-uniform: kept in LDS (broadcast ds_reads) rather
   // than in ~26 VGPRs; measured 2.12 ms vs 2.30 (asm memory clobber) and
   // 2.48 ms (volatile reload) per 1e8 rays.
@@ -541,6 +548,7 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
   }
   if (tid == 0) {
     s_tallied = 0u;
+    if constexpr (PLAINK) s_cold_n = 0u;
     s_next = (uint32_t)r_begin;
     s_emit = load_emitter(D, g);
     if (SINGLE) {
@@ -603,7 +611,9 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
     // share their blocks like every other group.  (One ray per lane for
     // them, each drawing its own block, needs a second loop with its own
     // code site for the ray; that form does not compile -- "illegal VGPR to
-    // SGPR copy" in the backend -- and was not measured.)
+    // SGPR copy" in the backend -- and was not measured.  The LAT ray's
+    // closed-enclosure copy below does have a second site, for its cold rays
+    // after the loop; it takes per-lane values only and compiles.)
     auto one_ray = [&](uint32_t r, bool have_pw, uint32_t pw, auto ek) {
       constexpr int EK = decltype(ek)::value;
       double ox, oy, px, py;
@@ -629,9 +639,27 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
     // live in the loop the fast body's registers no longer fit 64 VGPRs, and
     // the spilled form measured 1 % slower than segment_lat there,
     // profiles/round9/ab/regressions_first.log.)
+    // PLAINK: the instances for a closed enclosure on a lattice in cell order
+    // (lat_plain, rthx_device.h; the launcher picks them from the host's
+    // domain record, launch_trace_s).  They hold the PLAIN copy of
+    // lat_ray_fast alone: no coarse wall index, no solid bit, no lat_map, and
+    // no continuation in the loop.  A ray is a pure function of (g, r), so a
+    // cold lane keeps only r: it appends r to the row's list in LDS (s_cold)
+    // and tallies like a lost ray, and after the loop the workgroup traces
+    // the listed rays through segment_lat, the general exact path (below the
+    // loops).  With no start or end point to hand on, the copy also treats
+    // three rare conditions as cold instead of selecting for them (DEFER,
+    // rthx_device.h): no candidate wall, an exact tie of the coarse test, a
+    // free-path word 0.  The copy is an instance of its own, not a second
+    // pair of loops beside the general one: built into the general instances
+    // it cost their loops scalar registers, and an enclosure with an open
+    // wall ran 0.5 % slower (profiles/round19/INDEX.md).  Every other
+    // instance is the code it was.  Faithful sampling and a ray base that is
+    // not 0 have no such instance.
     const bool lat_identity = LATRAY && __builtin_amdgcn_readfirstlane(D.lat.identity) != 0;
     auto one_ray_lat = [&](uint32_t r, uint32_t pw, bool cold0, auto ek) {
       constexpr int EK = decltype(ek)::value;
+      constexpr bool PLAIN = PLAINK;
       const SingleCoarse RTHX_LDS* scl = lds_opaque(&s_single);
       const SingleCoarse& sc = *(const SingleCoarse*)scl;
       const double* tab = g_tab;
@@ -639,14 +667,28 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
       const Emitter& e = *(const Emitter*)em;
       const RayWords rw = ray_words<EK>(P, e, (uint32_t)g, r, true, pw, FAITHFUL);
       LatRay ry;
-      start_ray_w<UNIFORM, FAITHFUL, EK, true>(P, e, (const double*)tab, rw, ry.px, ry.py, ry.dx, ry.dy, ry.S, &sc);
+      bool w_zero = false;  // (PLAIN: the free-path word is 0)
+      if constexpr (PLAIN)
+        start_ray_w<UNIFORM, FAITHFUL, EK, true, true>(P, e, (const double*)tab, rw, ry.px, ry.py, ry.dx, ry.dy, ry.S,
+                                                       &sc, &w_zero);
+      else
+        start_ray_w<UNIFORM, FAITHFUL, EK, true>(P, e, (const double*)tab, rw, ry.px, ry.py, ry.dx, ry.dy, ry.S, &sc);
       const char RTHX_LDS* lat = lds_opaque(cl_base);
-      int a = lat_ray_fast<EK == kEmitVolRect>(D, P.eta, sc, lat, lat_identity, cold0, ry);
+      int a = lat_ray_fast<EK == kEmitVolRect, PLAIN, PLAIN>(D, P.eta, sc, lat, lat_identity, cold0, ry, w_zero);
+      // PLAIN: a cold ray leaves the loop.  Its index goes to the row's list
+      // (s_cold; a slot past the list's end is counted, not stored) and it
+      // tallies nothing here, like a lost ray; the workgroup traces the listed
+      // rays after the loop (below).  A cold0 lane appends nothing.
       auto fixup = [&]() {
         int a2 = -1;
         if (!cold0) {
-          a2 = lat_ray_fixup(D, sc, lat, lat_identity, ry);
-          if (a2 < 0) atomicSub(&s_tallied, 1u);
+          if constexpr (PLAIN) {
+            const uint32_t slot_c = atomicAdd(&s_cold_n, 1u);
+            if (slot_c < (uint32_t)kLatColdList) s_cold[slot_c] = r;
+          } else {
+            a2 = lat_ray_fixup(D, sc, lat, lat_identity, ry);
+            if (a2 < 0) atomicSub(&s_tallied, 1u);
+          }
         }
         return a2;
       };
@@ -728,7 +770,41 @@ __global__ __launch_bounds__(kMaxTraceThreads) RTHX_TRACE_WAVES void trace_excha
       }
     }
     };
-    if constexpr (!FAITHFUL) {
+    if constexpr (PLAINK) {
+      if (vrect)
+        rounds(EmitKind<kEmitVolRect>{});
+      else
+        rounds(EmitKind<kEmitAny>{});
+      // The cold rays of the PLAIN copy, one code site for all of them: each
+      // is traced from its index through the general exact path (segment_lat,
+      // as the instances that read a ray base trace every ray; the ray draws
+      // its own free-path block) and tallied; a lost one comes off s_tallied
+      // like the loop's.  More cold rays than the list holds: the row's tally
+      // and its lost count start again and every ray of the row takes this
+      // path, so none is lost or counted twice.
+      __syncthreads();
+      const uint32_t n_cold = s_cold_n;
+      const bool all = n_cold > (uint32_t)kLatColdList;
+      if (all) {  // (the barrier above ended every tally of the loop; s_cold_n no longer changes)
+        for (int64_t w = tid; w < n_words; w += nthr) hist[w] = 0u;
+        if (tid == 0) s_tallied = 0u;
+        __syncthreads();
+      }
+      const uint32_t n_again = all ? re - rb : n_cold;
+      for (uint32_t i = (uint32_t)tid; i < n_again; i += (uint32_t)nthr) {
+        const uint32_t r = all ? rb + i : s_cold[i];
+        double ox, oy, px, py;
+        const SingleCoarse RTHX_LDS* sc = lds_opaque(&s_single);
+        const double* tab = g_tab;
+        const Emitter RTHX_LDS* em = lds_opaque(&s_emit);
+        const Emitter& e = *(const Emitter*)em;
+        const RayWords rw = ray_words<kEmitAny>(P, e, (uint32_t)g, r, false, 0u, FAITHFUL);
+        const int a = trace_one_w<UNIFORM, FAITHFUL, SINGLE, AXIS, true, kEmitAny>(
+            D, P, e, *(const SingleCoarse*)sc, (const double*)tab, rw, ox, oy, px, py, lds_opaque(cl_base));
+        tally(a);
+        if (a < 0) atomicSub(&s_tallied, 1u);
+      }
+    } else if constexpr (!FAITHFUL) {
       if (vrect)
         rounds(EmitKind<kEmitVolRect>{});
       else
@@ -1370,13 +1446,13 @@ static int device_cus() {
 }
 
 template <bool UNIFORM, int TALLY, bool FAITHFUL, bool SINGLE, bool REC, bool SPLIT, bool AXIS, int CL = 0,
-          bool RBASE = false, bool MIRROR = false>
+          bool RBASE = false, bool MIRROR = false, bool PLAINK = false>
 static hipError_t launch_trace_t(const LaunchCfg& L) {
   // SINGLE kernels: a ray base that is not 0 runs the RBASE instance (the
   // others read TraceParams::ray_base as it is)
   if constexpr (SINGLE && !RBASE)
     if (L.P.ray_base != 0) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, SINGLE, REC, SPLIT, AXIS, CL, true>(L);
-  auto kern = trace_exchange_kernel<UNIFORM, TALLY, FAITHFUL, SINGLE, REC, SPLIT, AXIS, CL, RBASE, MIRROR>;
+  auto kern = trace_exchange_kernel<UNIFORM, TALLY, FAITHFUL, SINGLE, REC, SPLIT, AXIS, CL, RBASE, MIRROR, PLAINK>;
   const int64_t blocks = L.T.n_rows * (SPLIT ? L.T.split : 1);
   // (MLAT kernels: a 64-slot ray queue per wave behind the lattice)
   auto lds_for = [&](int t) { return L.lds_bytes + (CL == 2 && !SINGLE ? (size_t)t * kRaySlotBytes : 0); };
@@ -1443,6 +1519,10 @@ static hipError_t launch_trace_s(const LaunchCfg& L) {
   // SINGLE kernels with CL = 1: the lattice locate (LAT; axis-aligned only);
   // multi-polygon kernels: CL = 1 coarse mesh in LDS, 2 lattice (MLAT, axis only)
   if constexpr (AXIS) {
+    // (a closed enclosure's uniform LAT rows at ray base 0: the instance with the closed-enclosure copy)
+    if constexpr (UNIFORM && !FAITHFUL)
+      if (L.single && L.clds && L.lat_plain && L.P.ray_base == 0)
+        return launch_trace_t<UNIFORM, TALLY, FAITHFUL, true, false, SPLIT, AXIS, 1, false, false, true>(L);
     if (L.single && L.clds) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, true, false, SPLIT, AXIS, 1>(L);
     if (!L.single && L.clds == 2) return launch_trace_t<UNIFORM, TALLY, FAITHFUL, false, false, SPLIT, AXIS, 2>(L);
   }

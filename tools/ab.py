@@ -49,6 +49,9 @@ def main():
     ap.add_argument("--env", default="",
                     help="NAME=v1,v2,...: every library is also timed with each value of that knob "
                          "(RTHX_DEV_KNOBS is set; 'auto' leaves the knob unset)")
+    ap.add_argument("--open-wall", type=int, default=-1,
+                    help="the C2 square with this coarse wall (0 bottom, 1 right, 2 top, 3 left) open: its rays are "
+                         "lost there, and the LAT rows run the general copy of the LAT ray, not the closed-enclosure one")
     ap.add_argument("--with-pack", action="store_true",
                     help="time trace + pack (staged rows: row scan, part merge, CSR pack) instead of the trace kernel alone")
     ap.add_argument("--sets", default="",
@@ -62,6 +65,15 @@ def main():
         import helpers as H
 
         dom = H.greenhouse_domain()
+    elif args.open_wall >= 0:
+        from rthx import PolyVolume2D, RayTracingDomain2D
+
+        solid = [w != args.open_wall for w in range(4)]
+        face = PolyVolume2D([(0.0, 0.0), (1.0, 0.0), (1.0, 1.0), (0.0, 1.0)], solid, 1, 1.0, 0.0)
+        face.T_in_w = [1000.0, 0.0, 0.0, 0.0]
+        face.epsilon = [1.0] * 4
+        face.T_in_g = -1.0
+        dom = RayTracingDomain2D([face], [(args.ndim, args.ndim)])
     else:
         dom = bench.build_domain(args.ndim)
     flat = dom.flat()
