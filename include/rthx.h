@@ -743,6 +743,43 @@ int rthx_scene3d_stats(const rthx_scene3d* scene, int64_t* n_tri, int64_t* n_nod
  * same test and counts.  hull_tris / interior_tris: the triangles of each
  * kind (box hull). */
 int rthx_scene3d_hull(const rthx_scene3d* scene, int32_t* hull, int64_t* hull_tris, int64_t* interior_tris);
+/* Specular symmetry planes.  As rthx_scene3d_create_grouped
+ * (its five first arguments, NULL group included), with n_mirror planar
+ * polygons mirror_xyz[n_mirror][4][3] / mirror_nv[n_mirror] (3 or 4 vertices,
+ * checked like the others) that reflect rays instead of absorbing them, so
+ * that half, a quarter or an octant of a symmetric enclosure can be traced.
+ * n_mirror == 0 with NULL mirror arrays gives exactly the scene of
+ * rthx_scene3d_create_grouped.  With n_mirror > 0 a single polygon (n == 1)
+ * is a valid scene.
+ *  - Mirrors are not surfaces: they emit nothing and own no row or column;
+ *    the result's N is n.  They are two-sided and take no normal.  Each is a
+ *    coplanar group of its own.
+ *  - Nearest hit: searched over real and mirror triangles together.  Mirror
+ *    triangles have the highest triangle ids, so a tie on t at a seam goes to
+ *    the real polygon.
+ *  - Reflection: when the nearest hit is a mirror with unit plane normal n,
+ *    the ray's origin becomes o + t d, its direction d - 2 (d.n) n, and the
+ *    walk starts again over the whole scene.  From then on the ray skips that
+ *    mirror alone (until its next reflection), no longer its emitter's group:
+ *    it may come back to its own face, and F_ii != 0 is then correct -- the
+ *    view of the face's mirror image.
+ *  - A ray still travelling after 10,000 reflections is lost; lost_total and
+ *    lost_max_row count such rays together with rays that hit nothing.
+ *  - A ray stays a pure function of (seed, emitter, ray index): emitter
+ *    ranges, strides, row splits, both row-count forms and faithful sampling
+ *    work as without mirrors, bit-reproducibly.
+ *  - A scene with a mirror is traced by the plain BVH walk: rthx_scene3d_hull
+ *    reports *hull = 0, and rthx_scene3d_stats counts the mirror triangles in
+ *    n_tri.
+ * Bad mirror input (nv not 3 or 4, non-planar, zero area, non-finite,
+ * n_mirror < 0, NULL arrays with n_mirror > 0) is RTHX_EINVAL and no scene is
+ * created. */
+int rthx_scene3d_create_mirrored(const double* xyz, const int32_t* nv, const double* normal, const int32_t* group,
+                                 int64_t n, const double* mirror_xyz, const int32_t* mirror_nv, int64_t n_mirror,
+                                 int32_t device, rthx_scene3d** out);
+/* *n_mirror = mirrors of the scene (0 without), *n_mirror_tris their
+ * triangles (any pointer may be NULL). */
+int rthx_scene3d_mirrors(const rthx_scene3d* scene, int64_t* n_mirror, int64_t* n_mirror_tris);
 int rthx_trace_exchange_3d(rthx_scene3d* scene, const rthx_trace_args* args, rthx_result* res);
 
 #ifdef __cplusplus

@@ -38,13 +38,14 @@ struct rthx_scene3d {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  DevBuf polys, tris, nodes, tables, scene, faces, lines, hull_tris, cvx_planes, cvx_start, cvx_items;
+  DevBuf polys, tris, nodes, tables, scene, faces, lines, hull_tris, cvx_planes, cvx_start, cvx_items, mirror_n;
   rthx::DevScene3D S{};
   int64_t n_poly = 0;
+  int64_t n_mirror = 0, n_mirror_tris = 0;  // symmetry planes (rthx_scene3d_create_mirrored) and their triangles
   int64_t n_hull_tris = 0, n_in_tris = 0;  // box hull: hull / interior triangles
   bool convex_interior = false;             // box hull: the interior is one convex set (Emit3::convex)
-  int top_choice[24] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
-                        -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};  // LDS node-cache size per kernel variant (launch_trace3d)
+  int top_choice[32] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
+                        -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};  // LDS node-cache size per kernel variant (launch_trace3d)
   int64_t cvx_list_items = 0;  // convex enclosure: entries of the cube map's lists
   int ghist_choice[4] = {-1, -1, -1, -1};  // per (faithful, pack16, N, R): global-histogram form chosen (1) or not (0)
   int64_t ghist_key[4] = {-1, -1, -1, -1};
@@ -610,10 +611,22 @@ RTHX_EXPORT int rthx_scene3d_create(const double* xyz, const int32_t* nv, const 
 
 RTHX_EXPORT int rthx_scene3d_create_grouped(const double* xyz, const int32_t* nv, const double* normal,
                                             const int32_t* group, int64_t n, int32_t device, rthx_scene3d** out) {
+  return rthx_scene3d_create_mirrored(xyz, nv, normal, group, n, nullptr, nullptr, 0, device, out);
+}
+
+RTHX_EXPORT int rthx_scene3d_create_mirrored(const double* xyz, const int32_t* nv, const double* normal,
+                                             const int32_t* group, int64_t n, const double* mirror_xyz,
+                                             const int32_t* mirror_nv, int64_t n_mirror, int32_t device,
+                                             rthx_scene3d** out) {
   if (!out) return fail(RTHX_EINVAL, "null out");
   *out = nullptr;
-  if (!xyz || !nv || !normal || n < 2) return fail(RTHX_EINVAL, "null argument or fewer than 2 polygons");
-  if (n >= (int64_t(1) << 30)) return fail(RTHX_ERANGE, "too many polygons");
+  if (n_mirror < 0) return fail(RTHX_EINVAL, "mirror count must be >= 0");
+  if (n_mirror > 0 && (!mirror_xyz || !mirror_nv)) return fail(RTHX_EINVAL, "null mirror arrays with n_mirror > 0");
+  // (behind mirrors one polygon is an enclosure: it sees its own images)
+  if (!xyz || !nv || !normal || n < (n_mirror > 0 ? 1 : 2))
+    return fail(RTHX_EINVAL, "null argument or fewer than 2 polygons");
+  if (n >= (int64_t(1) << 30) || n_mirror >= (int64_t(1) << 30) || n + n_mirror >= (int64_t(1) << 30))
+    return fail(RTHX_ERANGE, "too many polygons");
   const double t_start = now_ms();
   // groups: each a contiguous run of polygon indices ([glo, ghi) per polygon)
   std::vector<int32_t> glo(n), ghi(n);
@@ -707,6 +720,66 @@ RTHX_EXPORT int rthx_scene3d_create_grouped(const double* xyz, const int32_t* nv
       bt.push_back(B);
     }
   }
+  // Symmetry planes: two-sided, no emission frame and no row; their triangles
+  // follow the real ones (the highest ids: a tie on t at a seam goes to the
+  // real polygon), polygon n + m, each a group of its own above every real
+  // group id.
+  int64_t mirror_group0 = 0;
+  for (int64_t k = 0; k < n; ++k) mirror_group0 = std::max<int64_t>(mirror_group0, (int64_t)polys[k].group + 1);
+  if (mirror_group0 + n_mirror >= (int64_t(1) << 31)) return fail(RTHX_ERANGE, "group ids leave no room for the mirror groups");
+  std::vector<double> mirror_n((size_t)(3 * n_mirror));
+  const size_t n_real_tris = tris.size();
+  for (int64_t k = 0; k < n_mirror; ++k) {
+    const int m = mirror_nv[k];
+    if (m != 3 && m != 4) return fail(RTHX_EINVAL, "mirror polygon with n not in {3,4}");
+    const double* p = mirror_xyz + 12 * k;
+    for (int i = 0; i < 3 * m; ++i)
+      if (!std::isfinite(p[i])) return fail(RTHX_EINVAL, "non-finite mirror vertex");
+    V v[4];
+    for (int i = 0; i < 4; ++i) {
+      const int j = i < m ? i : m - 1;
+      v[i] = {p[3 * j], p[3 * j + 1], p[3 * j + 2]};
+      for (int d = 0; d < 3; ++d) {
+        slo[d] = std::min(slo[d], p[3 * j + d]);
+        shi[d] = std::max(shi[d], p[3 * j + d]);
+      }
+    }
+    const V ng = cross(sub(v[1], v[0]), sub(v[2], v[0]));
+    const double a1 = norm(ng) / 2;
+    const double a2 = m == 4 ? norm(cross(sub(v[3], v[2]), sub(v[0], v[2]))) / 2 : 0.0;
+    if (!(a1 > 0.0) || (m == 4 && !(a2 > 0.0))) return fail(RTHX_EINVAL, "degenerate mirror polygon (zero area)");
+    const V nn = scale(ng, 1.0 / norm(ng));
+    if (m == 4) {  // planarity within 1e-9 of the polygon size
+      const double size = std::max(norm(sub(v[2], v[0])), norm(sub(v[3], v[1])));
+      if (std::fabs(dot(nn, sub(v[3], v[0]))) > 1e-9 * size)
+        return fail(RTHX_EINVAL, "mirror quad vertices are not coplanar");
+    }
+    mirror_n[(size_t)(3 * k)] = nn.x;
+    mirror_n[(size_t)(3 * k + 1)] = nn.y;
+    mirror_n[(size_t)(3 * k + 2)] = nn.z;
+    const int corners[2][3] = {{0, 1, 2}, {2, 3, 0}};
+    for (int h = 0; h < (m == 4 ? 2 : 1); ++h) {
+      const V a = v[corners[h][0]], b = v[corners[h][1]], c = v[corners[h][2]];
+      rthx::Tri3 T{};
+      const V e1 = sub(b, a), e2 = sub(c, a);
+      T.v0[0] = a.x; T.v0[1] = a.y; T.v0[2] = a.z;
+      T.e1[0] = e1.x; T.e1[1] = e1.y; T.e1[2] = e1.z;
+      T.e2[0] = e2.x; T.e2[1] = e2.y; T.e2[2] = e2.z;
+      T.poly = (int32_t)(n + k);
+      T.id = (int32_t)tris.size();
+      tris.push_back(T);
+      BuildTri B{};
+      for (int d = 0; d < 3; ++d) {
+        const double x[3] = {d == 0 ? a.x : d == 1 ? a.y : a.z, d == 0 ? b.x : d == 1 ? b.y : b.z,
+                             d == 0 ? c.x : d == 1 ? c.y : c.z};
+        B.lo[d] = std::min({x[0], x[1], x[2]});
+        B.hi[d] = std::max({x[0], x[1], x[2]});
+        B.c[d] = (x[0] + x[1] + x[2]) / 3.0;
+      }
+      B.group = (int32_t)(mirror_group0 + k);
+      bt.push_back(B);
+    }
+  }
   // fp32 box padding: covers the rounding of the fp32 slab test for any ray
   // that stays within the scene scale
   double scale = 0.0;
@@ -727,7 +800,8 @@ RTHX_EXPORT int rthx_scene3d_create_grouped(const double* xyz, const int32_t* nv
   HullBuild hb;
   double ball[4] = {0.0, 0.0, 0.0, 0.0};
   const char* no_hull = rthx::knob("RTHX_T3_NO_HULL");
-  const bool hull = group && !(no_hull && no_hull[0] == '1') && detect_box_hull(polys, n, slo, shi, hb);
+  // (a scene with a mirror is traced by the plain walk: no box hull, no exit-direction map -- DESIGN.md §7k)
+  const bool hull = n_mirror == 0 && group && !(no_hull && no_hull[0] == '1') && detect_box_hull(polys, n, slo, shi, hb);
   std::vector<rthx::Tri3> hull_tris;
   bool interior_convex = false;  // (box hull: the interior pass's finding, whatever the polygon order)
   int32_t full_root = 0, n_in_nodes = (int32_t)nodes.size();
@@ -815,7 +889,7 @@ RTHX_EXPORT int rthx_scene3d_create_grouped(const double* xyz, const int32_t* nv
   // directions (rthx_trace3d.h CvxPlane)
   CvxBuild cvb;
   const char* no_cvx = rthx::knob("RTHX_T3_NO_CVX");
-  const bool cvx = !hull && !(no_cvx && no_cvx[0] == '1') && detect_convex_enclosure(polys, tris_sorted, scale, cvb);
+  const bool cvx = n_mirror == 0 && !hull && !(no_cvx && no_cvx[0] == '1') && detect_convex_enclosure(polys, tris_sorted, scale, cvb);
   std::vector<double> tables(rthx::kTableDoubles);
   rthx::fill_tables(tables.data());
 
@@ -825,6 +899,8 @@ RTHX_EXPORT int rthx_scene3d_create_grouped(const double* xyz, const int32_t* nv
   if (!s) return fail(RTHX_ENOMEM, "host allocation failed");
   s->device = device;
   s->n_poly = n;
+  s->n_mirror = n_mirror;
+  s->n_mirror_tris = (int64_t)(tris.size() - n_real_tris);
   s->n_hull_tris = (int64_t)hull_tris.size();
   s->convex_interior = hull && n_in_tris > 0 && interior_convex;
   s->n_in_tris = n_in_tris;
@@ -852,6 +928,8 @@ RTHX_EXPORT int rthx_scene3d_create_grouped(const double* xyz, const int32_t* nv
               !up(s->cvx_start, cvb.start.data(), cvb.start.size() * 4) ||
               !up(s->cvx_items, cvb.items.data(), std::max<size_t>(cvb.items.size(), 1) * 4)))
     return bail(fail(RTHX_ENOMEM, "uploading the 3D scene's exit-direction map"));
+  if (n_mirror > 0 && !up(s->mirror_n, mirror_n.data(), mirror_n.size() * 8))
+    return bail(fail(RTHX_ENOMEM, "uploading the 3D scene's mirror normals"));
   s->S.n_poly = (int32_t)n;
   s->S.n_tri = (int32_t)tris.size();
   s->S.n_nodes = (int32_t)nodes.size();
@@ -884,6 +962,9 @@ RTHX_EXPORT int rthx_scene3d_create_grouped(const double* xyz, const int32_t* nv
   s->S.cvx_start = cvx ? s->cvx_start.as<int32_t>() : nullptr;
   s->S.cvx_items = cvx ? s->cvx_items.as<int32_t>() : nullptr;
   s->cvx_list_items = cvx ? (int64_t)cvb.items.size() : 0;
+  s->S.n_real = (int32_t)n;
+  s->S.mirror_group0 = (int32_t)mirror_group0;
+  s->S.mirror_n = n_mirror > 0 ? s->mirror_n.as<double>() : nullptr;
   if (!up(s->scene, &s->S, sizeof(s->S))) return bail(fail(RTHX_ENOMEM, "uploading the 3D scene"));
   if (rthx::knob("RTHX_VERBOSE"))
     std::fprintf(stderr, "rthx_scene3d_create: host geometry + BVH %.2f ms, device setup + upload %.2f ms\n",
@@ -909,6 +990,13 @@ RTHX_EXPORT int rthx_scene3d_hull(const rthx_scene3d* sc, int32_t* hull, int64_t
   if (hull) *hull = sc->S.hull ? (sc->convex_interior ? 2 : 1) : sc->S.cvx ? 3 : 0;
   if (hull_tris) *hull_tris = sc->n_hull_tris;
   if (interior_tris) *interior_tris = sc->n_in_tris;
+  return RTHX_OK;
+}
+
+RTHX_EXPORT int rthx_scene3d_mirrors(const rthx_scene3d* sc, int64_t* n_mirror, int64_t* n_mirror_tris) {
+  if (!sc) return fail(RTHX_EINVAL, "null scene");
+  if (n_mirror) *n_mirror = sc->n_mirror;
+  if (n_mirror_tris) *n_mirror_tris = sc->n_mirror_tris;
   return RTHX_OK;
 }
 
@@ -1016,6 +1104,7 @@ RTHX_EXPORT int rthx_trace_exchange_3d(rthx_scene3d* sc, const rthx_trace_args* 
     L.top_choice = sc->top_choice;
     L.hull = use_hull;
     L.cvx = sc->S.cvx != 0;
+    L.mirror = sc->n_mirror > 0;  // (hull and cvx are then 0: rthx_scene3d_create_mirrored)
     // The global-histogram form when its LDS (the stacks alone) keeps more
     // workgroups resident than the LDS histogram's (RTHX_T3_GHIST=0/1 forces).
     const char* gh = rthx::knob("RTHX_T3_GHIST");

@@ -182,12 +182,23 @@ struct DevScene3D {
   const int32_t RTHX_GLOBAL* cvx_start;    // [6 res^2 + 1] list offsets per cell
   const CvxPlane RTHX_GLOBAL* cvx_planes;  // per list entry: its triangle's plane (inline)
   const int32_t RTHX_GLOBAL* cvx_items;    // per list entry: its triangle's index into `tris`
+  // Specular symmetry planes (rthx_scene3d_create_mirrored),
+  // appended so that no field above moves.  Polygons [0, n_real) absorb and
+  // emit; a triangle whose poly is n_real + m belongs to mirror m, which is
+  // the group mirror_group0 + m of its own and has the unit normal
+  // mirror_n[3 m ..].  Without mirrors n_real == n_poly and mirror_n is null.
+  int32_t n_real;
+  int32_t mirror_group0;
+  const double RTHX_GLOBAL* mirror_n;
 };
 
 constexpr uint32_t kTrace3dTag = 0x40000000u;  // Philox counter word 3 of the 3D tracer
 // Per-lane walk stack in LDS: the scene's inner-node depth of entries (a
 // deeper SAH tree is rebuilt with median splits; deeper still is an error).
 constexpr int kBvhStack = 32;
+// A ray still travelling after this many reflections off symmetry planes is
+// lost (the 2D walk's segment cap: two facing mirrors with nothing between).
+constexpr int kTrace3dMaxReflections = 10000;
 
 #ifndef RTHX_T3_THREADS
 #define RTHX_T3_THREADS 256
@@ -219,7 +230,8 @@ struct Trace3dLaunch {
   bool ghist;   // counts straight to the dense rows (no LDS histogram)
   bool hull;    // box hull fast path (DevScene3D::hull)
   bool cvx;     // convex-enclosure fast path (DevScene3D::cvx)
-  int* top_choice;  // [mode * 8 + ghist * 4 + faithful * 2 + pack16] (mode 0 plain, 1 hull, 2 cvx): LDS node-cache size (64 / 128), -1 = not chosen yet
+  bool mirror;  // the scene holds symmetry planes (DevScene3D::n_real < its polygons): MODE 0's MIRROR kernels
+  int* top_choice;  // [mode * 8 + ghist * 4 + faithful * 2 + pack16] (mode 0 plain, 1 hull, 2 cvx, 3 mirror): LDS node-cache size (64 / 128), -1 = not chosen yet
 };
 
 hipError_t launch_trace3d(const Trace3dLaunch& L);

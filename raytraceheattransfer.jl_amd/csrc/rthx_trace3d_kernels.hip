@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "rthx_device.h"
 #include "rthx_trace3d.h"
@@ -422,10 +423,16 @@ __device__ __forceinline__ void emit_ray(const Emit3& E, const double* tab, uint
 // MODE: 0 the BVH walk alone, 1 box hull (HULL), 2 convex enclosure seen
 // from inside (CVX: DevScene3D::cvx; rays the fast path does not take walk
 // the whole scene's BVH, root 0).
-template <bool FAITHFUL, bool PACK16, int TOP, bool GH = false, int MODE = 0>
+// MIRROR (MODE 0 only): the scene holds specular symmetry planes
+// (rthx_scene3d_create_mirrored): triangles of polygons
+// >= DevScene3D::n_real.  A ray whose nearest hit is one of them is reflected
+// there and walks the whole scene again, now skipping that mirror instead of
+// its emitter's group; after kTrace3dMaxReflections reflections it is lost.
+template <bool FAITHFUL, bool PACK16, int TOP, bool GH = false, int MODE = 0, bool MIRROR = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MODE == 1 ? kHullWaves : GH ? kGhWaves : kHistWaves))) void trace_exchange_3d_kernel(const DevScene3D* __restrict__ Sp,
                                                                                   TraceParams P, TallyParams T) {
   constexpr bool HULL = MODE == 1, CVX = MODE == 2;
+  static_assert(!MIRROR || MODE == 0, "mirror scenes are traced by the plain BVH walk");
   // dynamic LDS: [row histogram][walk stacks] (GH: the stacks only)
   extern __shared__ uint32_t hist[];
   __shared__ Bvh2Node s_top[TOP];
@@ -467,7 +474,33 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MODE =
   __syncthreads();
   uint32_t tallied = 0;
   // the emitter's coplanar group: its triangles are skipped, its subtrees pruned
-  const int grp = s_emit.group, glo = s_emit.glo, glen = s_emit.ghi - s_emit.glo;
+  // (MIRROR: per lane -- after a reflection the skipped group is that mirror alone)
+  std::conditional_t<MIRROR, int, const int> grp = s_emit.group, glo = s_emit.glo, glen = s_emit.ghi - s_emit.glo;
+  const int n_real = MIRROR ? S.n_real : 0;
+  int bounces = 0;  // (MIRROR) reflections of this lane's ray so far
+  // MIRROR: the walk of a ray that met a mirror first starts again from the
+  // reflection point (o + t d, d - 2 (d.n) n with the mirror's unit normal n);
+  // false when the ray is to be tallied (or, past the cap, lost).
+  auto reflect = [&](Walk& w) {
+    if (!MIRROR || w.best_poly < n_real || bounces >= kTrace3dMaxReflections) return false;
+    const int m = w.best_poly - n_real;
+    const double RTHX_GLOBAL* nm = S.mirror_n + 3 * m;
+    const double n0 = nm[0], n1 = nm[1], n2 = nm[2];
+    const double dn2 = 2.0 * __builtin_fma(w.d[0], n0, __builtin_fma(w.d[1], n1, w.d[2] * n2));
+    const double o[3] = {__builtin_fma(w.best_t, w.d[0], w.o[0]), __builtin_fma(w.best_t, w.d[1], w.o[1]),
+                         __builtin_fma(w.best_t, w.d[2], w.o[2])};
+    const double d[3] = {__builtin_fma(-dn2, n0, w.d[0]), __builtin_fma(-dn2, n1, w.d[1]),
+                         __builtin_fma(-dn2, n2, w.d[2])};
+    w.init(o, d);
+    w.node = S.full_root;
+    if constexpr (MIRROR) {
+      grp = S.mirror_group0 + m;
+      glo = n_real + m;
+      glen = 1;
+    }
+    ++bounces;
+    return true;
+  };
   const bool convex = HULL && s_emit.convex != 0;
   int RTHX_LDS* stk = (int RTHX_LDS*)(hist + trace3d_stack_offset(words)) + tid;
   // HULL: the six face records and the lattice lines behind the stacks
@@ -482,7 +515,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MODE =
     __syncthreads();
   }
   auto tally = [&](int a) {
-    if (a >= 0) {
+    if (a >= 0 && (!MIRROR || a < n_real)) {  // (MIRROR: a ray still at a mirror past the reflection cap is lost)
       if (GH)
         __hip_atomic_fetch_add(&dense[a], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       else if (PACK16)
@@ -549,6 +582,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MODE =
         bool deep;
         emit_ray<FAITHFUL>(*(const Emit3*)em, s_tab, (uint32_t)g, r, P.key0, P.key1, o, d, deep);
         w.init(o, d);
+        if constexpr (MIRROR) {  // (a new ray skips its emitter's group again)
+          grp = s_emit.group;
+          glo = s_emit.glo;
+          glen = s_emit.ghi - s_emit.glo;
+          bounces = 0;
+        }
         if (MODE == 0) w.node = S.full_root;  // (a box-hull scene whose hull records did not fit in LDS: the whole BVH)
         if (HULL)  // (a convex interior emitter's deep ray, or one that misses the interior's ball, meets no interior triangle: no walk)
           w.node = w.hull_hit(S, grp, hf, hl)
@@ -569,7 +608,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MODE =
       }
     }
     if (__ballot(live) == 0ull && (!DEFER || (drained && q_cnt == 0))) break;
-    if (live && !w.step(S, topo, n_top, grp, glo, glen, stk)) {
+    if (live && !w.step(S, topo, n_top, grp, glo, glen, stk) && !reflect(w)) {
       tally(w.best_poly);
       live = false;
     }
@@ -583,13 +622,19 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MODE =
                        P.key1, o, d, deep);
     Walk w;
     w.init(o, d);
+    if constexpr (MIRROR) {
+      grp = s_emit.group;
+      glo = s_emit.glo;
+      glen = s_emit.ghi - s_emit.glo;
+      bounces = 0;
+    }
     if (MODE == 0) w.node = S.full_root;
     if (HULL)
       w.node = w.hull_hit(S, grp, hf, hl)
                    ? (S.n_in_nodes > 0 && !(convex && deep) && w.meets_ball(S) ? 0 : kWalkDone)
                    : S.full_root;
     if (CVX && deep && w.convex_exit(S)) w.node = kWalkDone;
-    while (w.step(S, topo, n_top, grp, glo, glen, stk)) {
+    while (w.step(S, topo, n_top, grp, glo, glen, stk) || reflect(w)) {
     }
     tally(w.best_poly);
   }
@@ -609,24 +654,24 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MODE =
 
 namespace {
 
-template <bool FAITHFUL, bool PACK16, bool GH, int MODE>
+template <bool FAITHFUL, bool PACK16, bool GH, int MODE, bool MIRROR = false>
 hipError_t launch_variant(const Trace3dLaunch& L) {
   // The 128-node cache when it costs no workgroup per CU against the 64-node
   // one (occupancy queries are slow host calls: the choice is kept per scene
   // and kernel variant in L.top_choice).
-  int& top = L.top_choice[MODE * 8 + (GH ? 4 : 0) + (FAITHFUL ? 2 : 0) + (PACK16 ? 1 : 0)];
+  int& top = L.top_choice[(MIRROR ? 3 : MODE) * 8 + (GH ? 4 : 0) + (FAITHFUL ? 2 : 0) + (PACK16 ? 1 : 0)];
   if (top < 0) {
     int pc64 = 0, pc128 = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &pc64, (const void*)t3::trace_exchange_3d_kernel<FAITHFUL, PACK16, 64, GH, MODE>, t3::kThreads, L.lds_bytes);
+        &pc64, (const void*)t3::trace_exchange_3d_kernel<FAITHFUL, PACK16, 64, GH, MODE, MIRROR>, t3::kThreads, L.lds_bytes);
     if (e != hipSuccess) return e;
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &pc128, (const void*)t3::trace_exchange_3d_kernel<FAITHFUL, PACK16, 128, GH, MODE>, t3::kThreads, L.lds_bytes);
+        &pc128, (const void*)t3::trace_exchange_3d_kernel<FAITHFUL, PACK16, 128, GH, MODE, MIRROR>, t3::kThreads, L.lds_bytes);
     if (e != hipSuccess) return e;
     top = pc128 > 0 && pc128 >= pc64 ? 128 : 64;
   }
-  auto kern = top == 128 ? t3::trace_exchange_3d_kernel<FAITHFUL, PACK16, 128, GH, MODE>
-                         : t3::trace_exchange_3d_kernel<FAITHFUL, PACK16, 64, GH, MODE>;
+  auto kern = top == 128 ? t3::trace_exchange_3d_kernel<FAITHFUL, PACK16, 128, GH, MODE, MIRROR>
+                         : t3::trace_exchange_3d_kernel<FAITHFUL, PACK16, 64, GH, MODE, MIRROR>;
   if (L.lds_bytes > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
     if (e != hipSuccess) return e;
@@ -638,32 +683,36 @@ hipError_t launch_variant(const Trace3dLaunch& L) {
 
 }  // namespace
 
-template <int MODE>
+template <int MODE, bool MIRROR = false>
 hipError_t launch_trace3d_h(const Trace3dLaunch& L) {
-  if (L.ghist) return L.faithful ? launch_variant<true, false, true, MODE>(L) : launch_variant<false, false, true, MODE>(L);
-  if (L.faithful) return L.pack16 ? launch_variant<true, true, false, MODE>(L) : launch_variant<true, false, false, MODE>(L);
-  return L.pack16 ? launch_variant<false, true, false, MODE>(L) : launch_variant<false, false, false, MODE>(L);
+  if (L.ghist)
+    return L.faithful ? launch_variant<true, false, true, MODE, MIRROR>(L) : launch_variant<false, false, true, MODE, MIRROR>(L);
+  if (L.faithful)
+    return L.pack16 ? launch_variant<true, true, false, MODE, MIRROR>(L) : launch_variant<true, false, false, MODE, MIRROR>(L);
+  return L.pack16 ? launch_variant<false, true, false, MODE, MIRROR>(L) : launch_variant<false, false, false, MODE, MIRROR>(L);
 }
 
 hipError_t launch_trace3d(const Trace3dLaunch& L) {
+  if (L.mirror) return launch_trace3d_h<0, true>(L);  // (planned as MODE 0: rthx_trace_exchange_3d)
   return L.hull ? launch_trace3d_h<1>(L) : L.cvx ? launch_trace3d_h<2>(L) : launch_trace3d_h<0>(L);
 }
 
 // Resident workgroups per CU of the LDS-histogram and the global-histogram
 // forms (the host keeps the global one when it fits more).
-template <int MODE>
+template <int MODE, bool MIRROR = false>
 void occupancy_kernels(const Trace3dLaunch& L, const void** kh, const void** kg) {
-  *kh = L.faithful ? (L.pack16 ? (const void*)t3::trace_exchange_3d_kernel<true, true, 64, false, MODE>
-                               : (const void*)t3::trace_exchange_3d_kernel<true, false, 64, false, MODE>)
-                   : (L.pack16 ? (const void*)t3::trace_exchange_3d_kernel<false, true, 64, false, MODE>
-                               : (const void*)t3::trace_exchange_3d_kernel<false, false, 64, false, MODE>);
-  *kg = L.faithful ? (const void*)t3::trace_exchange_3d_kernel<true, false, 64, true, MODE>
-                   : (const void*)t3::trace_exchange_3d_kernel<false, false, 64, true, MODE>;
+  *kh = L.faithful ? (L.pack16 ? (const void*)t3::trace_exchange_3d_kernel<true, true, 64, false, MODE, MIRROR>
+                               : (const void*)t3::trace_exchange_3d_kernel<true, false, 64, false, MODE, MIRROR>)
+                   : (L.pack16 ? (const void*)t3::trace_exchange_3d_kernel<false, true, 64, false, MODE, MIRROR>
+                               : (const void*)t3::trace_exchange_3d_kernel<false, false, 64, false, MODE, MIRROR>);
+  *kg = L.faithful ? (const void*)t3::trace_exchange_3d_kernel<true, false, 64, true, MODE, MIRROR>
+                   : (const void*)t3::trace_exchange_3d_kernel<false, false, 64, true, MODE, MIRROR>;
 }
 
 hipError_t trace3d_occupancy(const Trace3dLaunch& L, size_t lds_hist, size_t lds_gh, int* wg_hist, int* wg_gh) {
   const void *kh = nullptr, *kg = nullptr;
-  if (L.hull) occupancy_kernels<1>(L, &kh, &kg);
+  if (L.mirror) occupancy_kernels<0, true>(L, &kh, &kg);
+  else if (L.hull) occupancy_kernels<1>(L, &kh, &kg);
   else if (L.cvx) occupancy_kernels<2>(L, &kh, &kg);
   else occupancy_kernels<0>(L, &kh, &kg);
   hipError_t e = hipSuccess;

@@ -571,7 +571,7 @@ function enclosureViewFactors3D(superFaces, parallel::Bool, max_iters::Int = 100
 end
 
 """
-    enclosureViewFactorsMC3D(superFaces, rays_tot; max_iters=1000)
+    enclosureViewFactorsMC3D(superFaces, rays_tot; max_iters=1000, mirrors=nothing)
 
 Monte Carlo counterpart of enclosureViewFactors3D for enclosures with
 obstructions (BASELINE config 4: a sphere inside a cube), where the analytic
@@ -583,8 +583,15 @@ absorbed by its own face).
 (parallelRayTracing.jl:6).  F_raw = counts / R, row-normalised like the 2D
 path (row_normalize!), then the reference's smooth_F with
 smooth_surfaces_only = true (enclosureViewFactors3D.jl:88-91).
+
+`mirrors`: specular symmetry planes (rthx_scene3d_create_mirrored), a vector
+of planar polygons, each a vector of 3 or 4 points.  They reflect rays, are
+no sub-faces and own no row or column of F, so half, a quarter or an octant
+of a symmetric enclosure can be modelled; a sub-face then sees its own mirror
+image (F_ii != 0).  `nothing` or empty: no mirrors.
 """
-function enclosureViewFactorsMC3D(superFaces, rays_tot::Integer; max_iters::Int = 1000, verbose::Bool = false)
+function enclosureViewFactorsMC3D(superFaces, rays_tot::Integer; max_iters::Int = 1000, verbose::Bool = false,
+                                  mirrors = nothing)
     RTHT = parentmodule(@__MODULE__).RayTraceHeatTransfer
     subs = [sf for f in superFaces for sf in f.subFaces]
     # the sub-faces of one super face are coplanar: one group (contiguous, face-major)
@@ -602,9 +609,24 @@ function enclosureViewFactorsMC3D(superFaces, rays_tot::Integer; max_iters::Int 
     end
     R = div(rays_tot, n)
     scene = Ref{Ptr{Cvoid}}(C_NULL)
-    check(ccall((:rthx_scene3d_create_grouped, LIB[]), Cint,
-                (Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Int64, Int32, Ptr{Ptr{Cvoid}}),
-                xyz, nv, nrm, grp, n, DEVICE[], scene))
+    nm = mirrors === nothing ? 0 : length(mirrors)
+    if nm == 0
+        check(ccall((:rthx_scene3d_create_grouped, LIB[]), Cint,
+                    (Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Int64, Int32, Ptr{Ptr{Cvoid}}),
+                    xyz, nv, nrm, grp, n, DEVICE[], scene))
+    else
+        mxyz = zeros(Float64, 12nm); mnv = zeros(Int32, nm)
+        for (k, P) in enumerate(mirrors)
+            mnv[k] = length(P)
+            for (i, v) in enumerate(P), d in 1:3
+                mxyz[12(k - 1) + 3(i - 1) + d] = v[d]
+            end
+        end
+        check(ccall((:rthx_scene3d_create_mirrored, LIB[]), Cint,
+                    (Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Int64, Ptr{Float64}, Ptr{Int32}, Int64, Int32,
+                     Ptr{Ptr{Cvoid}}),
+                    xyz, nv, nrm, grp, n, mxyz, mnv, nm, DEVICE[], scene))
+    end
     res = Ref{Ptr{Cvoid}}(C_NULL)
     try
         check(ccall((:rthx_result_create, LIB[]), Cint, (Ptr{Ptr{Cvoid}},), res))

@@ -336,6 +336,8 @@ EXPORTED_SYMBOLS = (
     "rthx_scene3d_destroy",
     "rthx_scene3d_stats",
     "rthx_scene3d_hull",
+    "rthx_scene3d_create_mirrored",
+    "rthx_scene3d_mirrors",
     "rthx_trace_exchange_3d",
 )
 

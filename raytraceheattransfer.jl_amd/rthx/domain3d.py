@@ -172,9 +172,21 @@ class ViewFactorDomain3D:
     (ViewFactorDomain3D.jl:2-89).  ``faces`` holds 1-based vertex indices as in
     the reference."""
 
-    def __init__(self, points, faces, Ndims: int, q_in_w, T_in_w, epsilon):
+    def __init__(self, points, faces, Ndims: int, q_in_w, T_in_w, epsilon, mirror_faces=None):
         points = np.asarray(points, dtype=np.float64)
         faces = np.asarray(faces, dtype=np.int64) - 1
+        # mirror_faces (an extension): rows of 1-based vertex indices like
+        # `faces`, the enclosure's specular symmetry planes.  They are not
+        # meshed and are no elements; method="montecarlo" hands them to the
+        # tracer (rthx.trace3d, DESIGN.md §7k).
+        self.mirror_faces = []
+        for row in ([] if mirror_faces is None else mirror_faces):
+            idx = [int(j) - 1 for j in row]
+            if len(idx) not in (3, 4):
+                raise ValueError("mirror_faces: every mirror face has 3 or 4 vertex indices")
+            if min(idx) < 0 or max(idx) >= len(points):
+                raise ValueError("mirror_faces: vertex index out of range (indices are 1-based)")
+            self.mirror_faces.append(idx)
         is_spectral = isinstance(epsilon[0], (list, np.ndarray))
         if is_spectral:
             spread = np.std([np.std(e) for e in epsilon])
@@ -231,6 +243,17 @@ class ViewFactorDomain3D:
             xyz[k, : nv[k]] = np.array(s.vertices)
         return xyz, nv
 
+    def mirror_arrays(self):
+        """(mxyz[m][4][3], mnv[m]) of the mirror faces, or None without any."""
+        if not self.mirror_faces:
+            return None
+        mxyz = np.zeros((len(self.mirror_faces), 4, 3))
+        mnv = np.zeros(len(self.mirror_faces), dtype=np.int32)
+        for k, idx in enumerate(self.mirror_faces):
+            mnv[k] = len(idx)
+            mxyz[k, : len(idx)] = self.points[idx]
+        return mxyz, mnv
+
     def __call__(self, parallel: bool = True, max_iters: int = 1000, device: int = 0, verbose: bool = False,
                  method: str = "analytic", rays_tot: int = 0, seed: int = 1):
         """ViewFactorDomain3D functor (ViewFactorDomain3D.jl:92-101) ->
@@ -238,9 +261,14 @@ class ViewFactorDomain3D:
         device, sub-face areas from viewFactor3D's formulas, then smooth_F with
         smooth_surfaces_only = true.  ``method="montecarlo"`` (an extension:
         enclosures with obstructions) traces ``rays_tot`` rays instead
-        (rthx.trace3d, rays leave along each sub-face's inward normal)."""
+        (rthx.trace3d, rays leave along each sub-face's inward normal); the
+        domain's mirror faces reflect them.  The analytic view factors know no
+        reflection: with mirror faces ``method="analytic"`` is a ValueError."""
         from .smoothing import smooth_F
 
+        if self.mirror_faces and method == "analytic":
+            raise ValueError("a domain with mirror_faces needs method='montecarlo': the analytic view factors "
+                             "cannot represent a reflection")
         xyz, nv = self.polygon_arrays()
         if method == "montecarlo":
             from .trace3d import exchange_factors_3d
@@ -248,7 +276,8 @@ class ViewFactorDomain3D:
             _, area, _ = view_factors_3d(xyz, nv, device=device, with_F=False)
             normals = np.array([s.inwardNormal for s in self.subfaces()])
             R = max(1, int(rays_tot) // len(nv))
-            F_raw = exchange_factors_3d(xyz, nv, normals, R, seed=seed, device=device).toarray()
+            F_raw = exchange_factors_3d(xyz, nv, normals, R, seed=seed, device=device,
+                                        mirrors=self.mirror_arrays()).toarray()
             info = {"rays_per_emitter": R}
         elif method == "analytic":
             F_raw, area, info = view_factors_3d(xyz, nv, device=device)

@@ -20,20 +20,49 @@ import scipy.sparse as sp
 from . import abi
 
 
-class Scene3D:
-    """An uploaded 3D polygon scene (rthx_scene3d*)."""
+def mirror_arrays(mirrors):
+    """``mirrors = (mxyz, mnv)`` as the contiguous arrays
+    rthx_scene3d_create_mirrored takes: mxyz[m][4][3] float64 (a triangle's
+    fourth vertex unused) and mnv[m] int32, each 3 or 4.  ValueError on a
+    shape or count that cannot be a list of polygons (no device needed)."""
+    try:
+        mxyz, mnv = mirrors
+    except (TypeError, ValueError):
+        raise ValueError("mirrors must be a pair (mxyz[m][4][3], mnv[m])") from None
+    k = np.ascontiguousarray(mnv, dtype=np.int32).reshape(-1)
+    x = np.ascontiguousarray(mxyz, dtype=np.float64)
+    if x.size != 12 * len(k):
+        raise ValueError(f"mirrors: mxyz holds {x.size} numbers, {len(k)} polygons need {12 * len(k)}")
+    if np.any((k != 3) & (k != 4)):
+        raise ValueError("mirrors: every mirror polygon has 3 or 4 vertices")
+    return x.reshape(-1, 12), k
 
-    def __init__(self, xyz, nv, normals, device: int = 0, groups=None):
+
+class Scene3D:
+    """An uploaded 3D polygon scene (rthx_scene3d*).  ``mirrors = (mxyz, mnv)``:
+    specular symmetry planes (rthx_scene3d_create_mirrored) --
+    planar polygons that reflect rays and own no row or column."""
+
+    def __init__(self, xyz, nv, normals, device: int = 0, groups=None, mirrors=None):
         from ._lib import check, load
 
-        self._lib = load()
-        self.device = device
         x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 12)
         k = np.ascontiguousarray(nv, dtype=np.int32)
         nrm = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
+        m = None if mirrors is None else mirror_arrays(mirrors)
+        self._lib = load()
+        self.device = device
         self.n = len(k)
         h = C.c_void_p()
-        if groups is None:
+        if m is not None:
+            mx, mk = m
+            g = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+            check(self._lib.rthx_scene3d_create_mirrored(
+                abi.ptr(x, C.c_double), abi.ptr(k, C.c_int32), abi.ptr(nrm, C.c_double),
+                None if g is None else abi.ptr(g, C.c_int32), self.n,
+                abi.ptr(mx, C.c_double) if len(mk) else None, abi.ptr(mk, C.c_int32) if len(mk) else None, len(mk),
+                device, C.byref(h)))
+        elif groups is None:
             check(self._lib.rthx_scene3d_create(abi.ptr(x, C.c_double), abi.ptr(k, C.c_int32),
                                                 abi.ptr(nrm, C.c_double), self.n, device, C.byref(h)))
         else:  # coplanar groups: rays are never absorbed by their emitter's group
@@ -96,6 +125,14 @@ class Scene3D:
                        hull_mode=h.value, hull_tris=ht.value, interior_tris=it.value)
         return out
 
+    def mirrors(self) -> dict:
+        """rthx_scene3d_mirrors: the scene's symmetry planes and their triangles."""
+        from ._lib import check
+
+        nm, nt = C.c_int64(), C.c_int64()
+        check(self._lib.rthx_scene3d_mirrors(self.handle, C.byref(nm), C.byref(nt)))
+        return {"n_mirror": nm.value, "n_mirror_tris": nt.value}
+
     def close(self) -> None:
         if getattr(self, "handle", None):
             self._lib.rthx_scene3d_destroy(self.handle)
@@ -109,10 +146,10 @@ class Scene3D:
 
 
 def exchange_factors_3d(xyz, nv, normals, rays_per_emitter: int, seed: int = 1, device: int = 0,
-                        faithful: bool = False) -> sp.csr_matrix:
+                        faithful: bool = False, mirrors=None) -> sp.csr_matrix:
     """F_raw (CSR, rows = emitters) = counts / R, as the 2D tracer's
-    counts_to_F (parallelRayTracing.jl:145)."""
-    scene = Scene3D(xyz, nv, normals, device)
+    counts_to_F (parallelRayTracing.jl:145).  ``mirrors``: as Scene3D's."""
+    scene = Scene3D(xyz, nv, normals, device, mirrors=mirrors)
     try:
         rp, cols, cnt, _info = scene.trace(rays_per_emitter, seed=seed, faithful=faithful)
     finally:
