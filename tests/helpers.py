@@ -188,6 +188,32 @@ def counts_matrix(row_ptr, cols, counts, n):
     return sp.csr_matrix((counts.astype(np.float64), cols.astype(np.int64), row_ptr.astype(np.int64)), shape=(n, n))
 
 
+def dense(rp, cols, cnt, n):
+    return np.asarray(counts_matrix(rp, cols, cnt, n).todense())
+
+
+def homogeneity(A, B, min_bin=40):
+    """Sum over rows of the two-sample homogeneity statistic
+    X2 = sum_j (sqrt(Nb/Na) a_j - sqrt(Na/Nb) b_j)^2 / (a_j + b_j) (Na, Nb the
+    row totals), columns with a_j + b_j < min_bin pooled into one bin; and its
+    degrees of freedom, sum over rows of (bins - 1)."""
+    x2, dof = 0.0, 0
+    for a, b in zip(np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)):
+        small = a + b < min_bin
+        a = np.append(a[~small], a[small].sum())
+        b = np.append(b[~small], b[small].sum())
+        keep = a + b > 0
+        a, b = a[keep], b[keep]
+        na, nb = a.sum(), b.sum()
+        if na == 0 or nb == 0:  # (a row without a tallied ray on one side: every bin disagrees)
+            x2 += na + nb
+            dof += max(len(a) - 1, 0)
+            continue
+        x2 += float(np.sum((math.sqrt(nb / na) * a - math.sqrt(na / nb) * b) ** 2 / (a + b)))
+        dof += len(a) - 1
+    return x2, dof
+
+
 def surface_segments(dom):
     """[(a, b)] end points of every surface element, CCW along its polygon."""
     segs = [None] * dom.num_surfaces

@@ -25,6 +25,7 @@ import scipy.special
 import scipy.stats
 
 import helpers as H
+from helpers import dense, homogeneity
 from oracle import oracle
 from rthx import PolyVolume2D, RayTracingDomain2D, abi
 
@@ -152,37 +153,11 @@ def gpu_counts(hip, dom, R, seed=1, ray_begin=0, **kw):
         dd.close()
 
 
-def dense(rp, cols, cnt, n):
-    return np.asarray(H.counts_matrix(rp, cols, cnt, n).todense())
-
-
 def assert_same_counts(a, b, what=""):
     for k, name in enumerate(("row_ptr", "cols", "counts")):
         assert np.array_equal(a[k], b[k]), f"{what}: {name} differ"
     for k in ("rays_traced", "rows_traced", "nnz", "lost_total", "lost_max_row"):
         assert a[3][k] == b[3][k], (what, k, a[3][k], b[3][k])
-
-
-def homogeneity(A, B, min_bin=40):
-    """Sum over rows of the two-sample homogeneity statistic
-    X2 = sum_j (sqrt(Nb/Na) a_j - sqrt(Na/Nb) b_j)^2 / (a_j + b_j) (Na, Nb the
-    row totals), columns with a_j + b_j < min_bin pooled into one bin; and its
-    degrees of freedom, sum over rows of (bins - 1)."""
-    x2, dof = 0.0, 0
-    for a, b in zip(np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)):
-        small = a + b < min_bin
-        a = np.append(a[~small], a[small].sum())
-        b = np.append(b[~small], b[small].sum())
-        keep = a + b > 0
-        a, b = a[keep], b[keep]
-        na, nb = a.sum(), b.sum()
-        if na == 0 or nb == 0:  # (a row without a tallied ray on one side: every bin disagrees)
-            x2 += na + nb
-            dof += max(len(a) - 1, 0)
-            continue
-        x2 += float(np.sum((math.sqrt(nb / na) * a - math.sqrt(na / nb) * b) ** 2 / (a + b)))
-        dof += len(a) - 1
-    return x2, dof
 
 
 FOLD_CASES = {
