@@ -42,7 +42,7 @@ extern "C" {
 #endif
 
 #define RTHX_ABI_VERSION 5  /* 5: rthx_trace_exchange_rays, rthx_result_accumulate[_csr], rthx_result_sampling_error */
-/* Functions added since (rthx_csr_symmetrize, rthx_smooth_get_build) change no
+/* Functions added since (rthx_csr_symmetrize, rthx_smooth_get_build, rthx_gasbox_*) change no
  * existing signature or struct: the version stays 5, and a caller that needs
  * them looks the symbols up. */
 
@@ -781,6 +781,72 @@ int rthx_scene3d_create_mirrored(const double* xyz, const int32_t* nv, const dou
  * triangles (any pointer may be NULL). */
 int rthx_scene3d_mirrors(const rthx_scene3d* scene, int64_t* n_mirror, int64_t* n_mirror_tris);
 int rthx_trace_exchange_3d(rthx_scene3d* scene, const rthx_trace_args* args, rthx_result* res);
+
+/* ------------------------------------------------------------------------
+ * 3D participating medium: exchange factors of a gas-filled box (DESIGN.md
+ * §7l) -- the furnace box of the zone method, the 3D analogue of the 2D
+ * tracer's uniform grey lattice.  The reference has no gas in 3D.
+ *
+ * Geometry.  An axis-aligned box lo[3] < hi[3] of n[3] >= 1 uniform cells per
+ * axis, h_a = (hi_a - lo_a) / n_a, filled with one grey medium of extinction
+ * beta = kappa + sigma_s >= 0 (given per trace).  All six faces are walls; the
+ * tracer absorbs at a wall, emissivity and albedo enter in the solve, as in
+ * 2D.
+ *
+ * Element order: surfaces first, then volumes.
+ *   - Faces f = 2 axis + side: x-, x+, y-, y+, z-, z+.  On a face of axis a,
+ *     with the other two axes p < q, cell (c_p, c_q) is element
+ *     face_offset[f] + c_p + n_p c_q.
+ *   - Volume (c_x, c_y, c_z) is element Ns + c_x + n_x (c_y + n_y c_z).
+ *   - Ns = 2 (n_y n_z + n_x n_z + n_x n_y), Nv = n_x n_y n_z, N = Ns + Nv.
+ *
+ * The ray (csrc/rthx_gasbox.h, shared by the kernel and the host check).
+ *   - Wall emitter: uniform point on its quad, cosine-law direction about the
+ *     inward normal (cos theta = sqrt(1 - u), uniform azimuth).  Volume
+ *     emitter: uniform point in its voxel, isotropic direction
+ *     (cos theta = 1 - 2u, uniform azimuth).
+ *   - Free path S = -ln(u) / beta, +inf for beta = 0.  Exit distance
+ *     t = min over the axes of ((d_a > 0 ? hi_a : lo_a) - o_a) / d_a (+inf
+ *     where d_a = 0; the lowest axis on a tie).
+ *   - Absorber: S < t, the voxel holding o + S d; otherwise the wall cell of
+ *     the exit face holding o + t d.  Cell index floor((x - lo) / h), clamped
+ *     to [0, n - 1].
+ *   - The box is closed: every ray is tallied, lost_total is always 0.
+ *   - A ray is a pure function of (seed, emitter, absolute ray id): emitter
+ *     ranges, strides, ray ranges and the kernel's row forms change no count.
+ * ------------------------------------------------------------------------ */
+typedef struct rthx_gasbox rthx_gasbox;
+
+/* Sizes of the lattice n alone (host only, no device): *n_surfaces = Ns,
+ * *n_volumes = Nv, face_offset[f] the first element of face f and
+ * face_offset[6] = Ns.  Any output may be NULL.  n NULL or some n < 1:
+ * RTHX_EINVAL. */
+int rthx_gasbox_layout(const int32_t n[3], int64_t* n_surfaces, int64_t* n_volumes, int64_t face_offset[7]);
+/* The box on `device`.  Checked before any device call: a NULL argument,
+ * n < 1, hi <= lo or a non-finite corner is RTHX_EINVAL; N >= 2^31 is
+ * RTHX_ERANGE. */
+int rthx_gasbox_create(const double lo[3], const double hi[3], const int32_t n[3], int32_t device,
+                       rthx_gasbox** out);
+void rthx_gasbox_destroy(rthx_gasbox* box);
+/* Traces ray ids ray_begin + [0, args->rays_per_emitter) of every emitter in
+ * args' range (emitter_begin, emitter_end, emitter_stride) through a medium
+ * of extinction beta into res, which then reads like a result of the other
+ * tracers: info, every copy, the device CSR, accumulate, the sampling error,
+ * the smoothing and the solves.  ray_begin = 0 is the plain trace; ranges of
+ * one seed accumulate to the one-shot trace bit for bit.
+ *   - args->flags: RTHX_FLAG_FAITHFUL_SAMPLING (plain fp64 log / cos / sin in
+ *     place of the table forms) and RTHX_FLAG_DEVICE_ONLY; any other flag is
+ *     RTHX_EINVAL.  bin must be 0 and n_record 0 (RTHX_EINVAL); nudge is
+ *     unused.
+ *   - Checked before any device call: a NULL argument, beta < 0 or not
+ *     finite, ray_begin < 0 (RTHX_EINVAL); ray_begin + rays_per_emitter >=
+ *     2^32 (RTHX_ERANGE: the kernel indexes rays in 32 bits).
+ *   - Staging: rows x N x 4 bytes of dense counts on the device, plus the
+ *     CSR.  A failed allocation is reported like the other tracers'
+ *     (RTHX_EDEVICE); trace a large lattice in emitter ranges and keep each
+ *     range's CSR. */
+int rthx_gasbox_trace(rthx_gasbox* box, const rthx_trace_args* args, double beta, int64_t ray_begin,
+                      rthx_result* res);
 
 #ifdef __cplusplus
 }

@@ -289,6 +289,13 @@ __device__ __forceinline__ void philox_words(uint32_t w0, uint32_t w1, uint32_t 
 // (w0, w1, blk, w3) -> a and (w0, w1, blk + 1, w3) -> c;
 //   R1 = u52(a0,a1)  R2 = u52(a2,a3)  path = u52(c0,c1)  sel = u32(c2)
 //   th = u32(c3)     ph = u32(a1[11:0]<<20 | a3[11:0]<<8 | c1[11:4])
+// The gas-box tracer (rthx_gasbox_kernels.hip, counter (ray id, emitter, 0 / 1,
+// gasbox::kTag)) reads the same two blocks as eight 32-bit draws u32(word):
+//   a0 a1 a2  position along x, y, z (a wall leaves its own axis' word unused)
+//   a3        polar angle: cos theta = sqrt(1 - u) (wall), 1 - 2u (volume)
+//   c0        azimuth 2 pi u
+//   c1        free path -ln(u) / beta (word 0: +inf)
+//   c2 c3     unused
 struct RayDraws {
   uint32_t a[4], c[4];
   // (w1, blk, w3 wave-uniform: philox_block_u)

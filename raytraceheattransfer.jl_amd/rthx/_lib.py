@@ -150,6 +150,13 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib.rthx_trace_exchange_3d.argtypes = [C.c_void_p, C.POINTER(abi.TraceArgs), C.c_void_p]
     lib.rthx_view_factors_3d.argtypes = [dp, C.POINTER(C.c_int32), C.c_int64, C.POINTER(abi.Vf3dArgs), dp, dp,
                                          C.POINTER(abi.Vf3dInfo)]
+    if hasattr(lib, "rthx_gasbox_trace"):  # (older A/B variant libraries lack these four)
+        lib.rthx_gasbox_layout.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_int64)]
+        lib.rthx_gasbox_create.argtypes = [dp, dp, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]
+        lib.rthx_gasbox_destroy.argtypes = [C.c_void_p]
+        lib.rthx_gasbox_destroy.restype = None
+        lib.rthx_gasbox_trace.argtypes = [C.c_void_p, C.POINTER(abi.TraceArgs), C.c_double, C.c_int64, C.c_void_p]
     if lib.rthx_abi_version() != abi.RTHX_ABI_VERSION:
         raise RthxError("librthx ABI version mismatch")
     _lib = lib

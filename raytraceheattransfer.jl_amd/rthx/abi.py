@@ -339,6 +339,10 @@ EXPORTED_SYMBOLS = (
     "rthx_scene3d_create_mirrored",
     "rthx_scene3d_mirrors",
     "rthx_trace_exchange_3d",
+    "rthx_gasbox_layout",
+    "rthx_gasbox_create",
+    "rthx_gasbox_destroy",
+    "rthx_gasbox_trace",
 )
 
 

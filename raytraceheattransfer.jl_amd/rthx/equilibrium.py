@@ -228,7 +228,10 @@ def solve_equilibrium(dom, F=None, device: int = 0, verbose: bool = False, max_i
     ignores max_iters and convergence_tol, as the reference's does); spectral
     domains take the spectral solve."""
     from .domain3d import ViewFactorDomain3D
+    from .gasbox import GasBox3D
 
+    if isinstance(dom, GasBox3D):  # (no counterpart in the reference: DESIGN.md §7l)
+        return equilibrium_gasbox(dom, device=dom.device if F is None else device, F=F, verbose=verbose)
     if isinstance(dom, ViewFactorDomain3D):  # solveEquilibrium.jl:13-22
         F3 = dom.F_smooth if F is None else F
         if dom.spectral_mode != "grey":
@@ -239,6 +242,60 @@ def solve_equilibrium(dom, F=None, device: int = 0, verbose: bool = False, max_i
         return equilibrium_spectral(dom, F, device=device, max_iters=max_iters, convergence_tol=convergence_tol,
                                     verbose=verbose)
     return equilibrium_grey(dom, F, device=device, verbose=verbose)
+
+
+def equilibrium_gasbox(box, device: int = 0, F=None, verbose: bool = False, info: Optional[dict] = None):
+    """The grey GERT solve of a GasBox3D (rthx.gasbox): E, b, coeff and h
+    assembled as equilibrium_grey assembles them (walls eps sigma A T^4, gas
+    4 kappa sigma V T^4, b = 1 - eps / omega), the system solved on the device
+    from the box's device-resident F_smooth (F: a matrix to use instead).
+    Writes T_w, q_w (per surface), T_g, q_g (per volume) and energy_error onto
+    the box -- an element with T given keeps it and gets q = emitted -
+    absorbed, one in radiative equilibrium keeps q and gets T -- and returns
+    (T, j, Abs, r) in element order."""
+    ns, nv = box.n_surfaces, box.n_volumes
+    n = ns + nv
+    area, vol = box.areas(), box.volume()
+    eps, kappa = box.epsilon, box.kappa
+    omega = box.sigma_s / box.beta if box.beta > 0.0 else 0.0
+    T_in = np.concatenate([box.T_in_w, box.T_in_g])
+    q_in = np.concatenate([box.q_in_w, box.q_in_g])
+    Q_known = (T_in < 0.0).astype(int)
+    size = np.concatenate([eps * area, np.full(nv, 4.0 * kappa * vol)])  # emission per sigma T^4
+    E = np.where(Q_known == 0, size * STEFAN_BOLTZMANN * np.where(Q_known == 0, T_in, 0.0) ** 4, 0.0)
+    b = np.zeros(n)
+    if omega > 1e-6 or np.sum(eps) < n:
+        b[:ns] = 1.0 - eps
+        b[ns:] = omega
+    h = np.where(Q_known == 1, q_in, E)
+    coeff = np.where(Q_known == 1, 1.0, b)
+    handle = None
+    if F is None:
+        handle = box.F_smooth_handle
+        if handle is None:
+            raise ValueError("the box has no F_smooth yet: call it (box(rays_tot)) before solve_equilibrium")
+    elif sp.issparse(F):
+        F = F.tocsr()[:n, :n]
+    else:
+        F = np.asarray(F)[:n, :n]
+    solve_info = {} if info is None else info
+    j, g = _solve(F, coeff, h, device, solve_info, handle=handle)
+    box.last_solve_info = solve_info
+    if verbose:
+        print(f"GMRES: {solve_info['iterations']} iterations in {solve_info['cycles']} cycles, "
+              f"residual {solve_info['residual']:.3e} (tolerance {solve_info['tolerance']:.3e})")
+    r = b * g
+    Abs = (1.0 - b) * g
+    e = np.maximum(j - r, 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        T = np.where(size > 0.0, (e / (size * STEFAN_BOLTZMANN)) ** 0.25, 0.0)
+    T = np.nan_to_num(T, nan=0.0)
+    T_out = np.where(Q_known == 1, T, T_in)
+    q_out = np.where(Q_known == 1, q_in, e - Abs)
+    box.T_w, box.q_w = T_out[:ns].copy(), q_out[:ns].copy()
+    box.T_g, box.q_g = T_out[ns:].copy(), q_out[ns:].copy()
+    box.energy_error = float(np.sum(j - r - Abs))
+    return T_out, j, Abs, r
 
 
 def equilibrium_surfaces_grey_3d(domain, F, spectral_bin: int = 1, device: int = 0, verbose: bool = False,
