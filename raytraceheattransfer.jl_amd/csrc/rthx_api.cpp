@@ -797,39 +797,6 @@ RTHX_EXPORT int rthx_result_create(rthx_result** out) {
 
 RTHX_EXPORT void rthx_result_destroy(rthx_result* res) { delete res; }
 
-namespace rthx {
-
-// Staged rows -> final CSR, after the trace launch on `st`: merge split rows
-// into the staging slots, scan the per-row nnz (row_off, totals), read the
-// totals back, size cols / counts to nnz and pack the slots.  totals[0..3] =
-// nnz, lost rays, max lost per row, look-back stalls (0 here).
-int finish_staged(rthx_result* res, const TallyParams& T, int merge, hipStream_t st, hipEvent_t ev_end,
-                  int64_t totals[4]) {
-  if (T.n_rows > 0) {
-    if (merge == kMergeDense) HIP_TRY(launch_compact(T, st), "row_compact_kernel launch");
-    if (merge == kMergeParts) HIP_TRY(launch_part_merge(T, st), "part_merge_kernel launch");
-    HIP_TRY(launch_scan(T.row_nnz, T.row_tallied, T.n_rows, T.R, res->row_off.as<int64_t>(),
-                        res->totals.as<int64_t>(), st),
-            "row_scan_kernel launch");
-  } else {
-    HIP_TRY(hipMemsetAsync(res->row_off.p, 0, 8, st), "hipMemset");
-  }
-  HIP_TRY(hipMemcpyAsync(totals, res->totals.p, 32, hipMemcpyDeviceToHost, st), "hipMemcpy totals");
-  HIP_TRY(hipStreamSynchronize(st), "row scan");
-  const size_t nnz = (size_t)std::max<int64_t>(totals[0], 1);
-  HIP_TRY(res->cols.reserve(nnz * 4), "hipMalloc cols");
-  HIP_TRY(res->cnt.reserve(nnz * 4), "hipMalloc cnt");
-  if (T.n_rows > 0)
-    HIP_TRY(launch_pack(T.stage_cols, T.stage_cnt, T.row_cap, res->row_off.as<int64_t>(), T.n_rows,
-                        res->cols.as<uint32_t>(), res->cnt.as<uint32_t>(), st),
-            "csr_pack_kernel launch");
-  HIP_TRY(hipEventRecord(ev_end, st), "hipEventRecord");
-  HIP_TRY(hipStreamSynchronize(st), "CSR pack");
-  return RTHX_OK;
-}
-
-}  // namespace rthx
-
 namespace {
 
 // Default bound on one look-back wait (100 MHz s_memrealtime ticks): a row
@@ -1193,30 +1160,10 @@ int trace_exchange_one(rthx_domain* dom, const rthx_trace_args* a, rthx_result* 
   int rc = plan_trace_split(dom, a, p);
   if (rc) return rc;
   if (res->device >= 0 && res->device != dom->device) return fail(RTHX_EINVAL, "result bound to another device");
-  for (rthx_result* q : res->parts) delete q;
-  res->parts.clear();
-  res->interleaved = false;
-  res->device = dom->device;
   const int64_t R = p.R, n_rows = p.n_rows;
-
-  res->valid = false;
-  res->host_rec = false;
-  res->host_row_off = false;
-  res->N = p.N;
-  res->R = R;
-  res->n_rows = n_rows;
-  res->begin = a->emitter_begin;
-  res->stride = a->emitter_stride;
-  res->split = p.split;
-  res->info = rthx_result_info{};
-  res->info.n_emitters = p.N;
-  res->info.rows_traced = n_rows;
-  res->info.rays_per_emitter = R;
-  res->info.rays_traced = n_rows * R;
-  res->info.n_devices = 1;
+  rthx::reset_result(res, dom->device, p.N, R, n_rows, a->emitter_begin, a->emitter_stride, p.split);
 
   // recorded emitters traced by this call (ascending, unique)
-  res->rec_g.clear();
   if (p.recording) {
     for (int i = 0; i < a->n_record; ++i) {
       const int64_t g = a->record_ids[i];

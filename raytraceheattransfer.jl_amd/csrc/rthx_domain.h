@@ -2,7 +2,8 @@
 // translation units: rthx_domain (the uploaded 2D domain, rthx_api.cpp
 // rthx_domain_create; used by the exchange tracer and the direct method,
 // rthx_direct.cpp) and rthx_result (an exchange trace's counts, filled by
-// rthx_trace_exchange and by the 3D tracer, rthx_trace3d.cpp).
+// rthx_trace_exchange and, through rthx_rowtrace.h, by the 3D tracer and the
+// gas-box tracer).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -144,9 +145,14 @@ namespace rthx {
 struct TallyParams;
 // How split rows are joined before the row scan (finish_staged).
 enum SplitMerge : int { kNoMerge = 0, kMergeDense = 1, kMergeParts = 2 };
-// rthx_api.cpp: staged rows -> final CSR after a trace launch on `st` (split
+// rthx_rowtrace.cpp: prepares `res` for a fresh one-device trace of this
+// shape: no parts, nothing valid or copied to the host, no recorded emitters,
+// the shape fields, and an info that is zero but for the shape.
+void reset_result(rthx_result* res, int device, int64_t N, int64_t R, int64_t n_rows, int64_t begin, int64_t stride,
+                  int64_t split);
+// rthx_rowtrace.cpp: staged rows -> final CSR after a trace launch on `st` (split
 // merge, row scan, totals read back, cols / counts sized to nnz, pack; ev_end
-// recorded after the pack).  Shared by the 2D and 3D tracers.
+// recorded after the pack).  Shared by the staged 2D path and the dense-row tracers.
 int finish_staged(rthx_result* res, const TallyParams& T, int merge, hipStream_t st, hipEvent_t ev_end,
                   int64_t totals[4]);
 // rthx_api.cpp: RTHX_OK when the result holds a trace that can be read (a

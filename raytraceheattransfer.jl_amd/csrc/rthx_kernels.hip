@@ -23,7 +23,7 @@
 //   the sum of the tallied count, and a row writer (hash row; split hand-off
 //   and histogram row).
 // row_compact_kernel: serves only the 3D tracer, whose split rows add into a
-//   dense per-row count buffer (rthx_trace3d.cpp finish_staged, kMergeDense).
+//   dense per-row count buffer (rthx_rowtrace.cpp finish_staged, kMergeDense).
 // part_merge_kernel: merges the sorted part lists of a split hash row.
 // row_scan_kernel: exclusive scan of per-row nnz + lost-ray reductions.
 // csr_pack_kernel: copies a staged launch's row slots into the dense CSR arrays.

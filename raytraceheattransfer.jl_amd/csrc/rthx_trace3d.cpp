@@ -10,7 +10,8 @@
 // slab tests never drop a hit the fp64 Moeller-Trumbore test would find) and
 // uploads it.  rthx_trace_exchange_3d traces R rays per emitter polygon into the
 // caller's rthx_result exactly like the 2D split-row path: dense per-row
-// counts, row_compact_kernel, row_scan_kernel, csr_pack_kernel.
+// counts, row_compact_kernel, row_scan_kernel, csr_pack_kernel (the sequence
+// of rthx_rowtrace.h around its own launch).
 #define RTHX_HOST_ONLY_TU 1
 #include <hip/hip_runtime.h>
 
@@ -27,7 +28,7 @@
 
 #include "../../include/rthx.h"
 #include "rthx_common.h"
-#include "rthx_domain.h"
+#include "rthx_rowtrace.h"
 #include "rthx_trace3d.h"
 
 using rthx::DevBuf;
@@ -35,10 +36,7 @@ using rthx::fail;
 using rthx::now_ms;
 
 struct rthx_scene3d {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  DevBuf polys, tris, nodes, tables, scene, faces, lines, hull_tris, cvx_planes, cvx_start, cvx_items, mirror_n;
+  DevBuf polys, tris, nodes, scene, faces, lines, hull_tris, cvx_planes, cvx_start, cvx_items, mirror_n;
   rthx::DevScene3D S{};
   int64_t n_poly = 0;
   int64_t n_mirror = 0, n_mirror_tris = 0;  // symmetry planes (rthx_scene3d_create_mirrored) and their triangles
@@ -49,12 +47,7 @@ struct rthx_scene3d {
   int64_t cvx_list_items = 0;  // convex enclosure: entries of the cube map's lists
   int ghist_choice[4] = {-1, -1, -1, -1};  // per (faithful, pack16, N, R): global-histogram form chosen (1) or not (0)
   int64_t ghist_key[4] = {-1, -1, -1, -1};
-  ~rthx_scene3d() {
-    (void)hipSetDevice(device);
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    // (stream: the device's shared stream, rthx::device_stream)
-  }
+  rthx::RowDevice dev;  // (last: destroyed first, so the buffers above are freed with its device current)
 };
 
 namespace {
@@ -75,8 +68,6 @@ constexpr int kLeafTris = RTHX_T3_LEAF;  // triangles per BVH leaf (at most)
 #ifndef RTHX_T3_SAH_BINS
 #define RTHX_T3_SAH_BINS 16
 #endif
-constexpr int64_t kSplitTargetBlocks = 16384;  // workgroups per launch (RTHX_T3_SPLIT_TARGET; 4096 / 8192 / 32768: slower at config 4)
-constexpr int64_t kSplitMinRays = 1024;
 
 struct BuildTri {
   double lo[3], hi[3], c[3];
@@ -890,14 +881,11 @@ RTHX_EXPORT int rthx_scene3d_create_mirrored(const double* xyz, const int32_t* n
   CvxBuild cvb;
   const char* no_cvx = rthx::knob("RTHX_T3_NO_CVX");
   const bool cvx = n_mirror == 0 && !hull && !(no_cvx && no_cvx[0] == '1') && detect_convex_enclosure(polys, tris_sorted, scale, cvb);
-  std::vector<double> tables(rthx::kTableDoubles);
-  rthx::fill_tables(tables.data());
 
   const double t_bvh = now_ms();
   RTHX_TRY(rthx::open_device(device, nullptr));  // (the stream: below, once the handle exists)
   rthx_scene3d* s = new (std::nothrow) rthx_scene3d();
   if (!s) return fail(RTHX_ENOMEM, "host allocation failed");
-  s->device = device;
   s->n_poly = n;
   s->n_mirror = n_mirror;
   s->n_mirror_tris = (int64_t)(tris.size() - n_real_tris);
@@ -908,17 +896,14 @@ RTHX_EXPORT int rthx_scene3d_create_mirrored(const double* xyz, const int32_t* n
     delete s;
     return code;
   };
-  if (rthx::device_stream(device, &s->stream) != hipSuccess) return bail(fail(RTHX_EDEVICE, "hipStreamCreate"));
-  for (auto& e : s->ev)
-    if (hipEventCreate(&e) != hipSuccess) return bail(fail(RTHX_EDEVICE, "hipEventCreate"));
+  if (const int rc = s->dev.open(device)) return bail(rc);
   auto up = [&](DevBuf& b, const void* src, size_t bytes) {
     if (b.reserve(bytes) != hipSuccess) return false;
     return hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
   };
   if (!up(s->polys, polys.data(), polys.size() * sizeof(rthx::Emit3)) ||
       !up(s->tris, tris_sorted.data(), tris_sorted.size() * sizeof(rthx::Tri3)) ||
-      !up(s->nodes, nodes.data(), nodes.size() * sizeof(rthx::Bvh2Node)) ||
-      !up(s->tables, tables.data(), tables.size() * 8))
+      !up(s->nodes, nodes.data(), nodes.size() * sizeof(rthx::Bvh2Node)))
     return bail(fail(RTHX_ENOMEM, "uploading the 3D scene"));
   if (hull && (!up(s->faces, hb.faces.data(), hb.faces.size() * sizeof(rthx::HullFace)) ||
                !up(s->lines, hb.lines.data(), hb.lines.size() * sizeof(float)) ||
@@ -937,7 +922,7 @@ RTHX_EXPORT int rthx_scene3d_create_mirrored(const double* xyz, const int32_t* n
   s->S.polys = s->polys.as<rthx::Emit3>();
   s->S.tris = s->tris.as<rthx::Tri3>();
   s->S.nodes = s->nodes.as<rthx::Bvh2Node>();
-  s->S.tables = s->tables.as<double>();
+  s->S.tables = s->dev.tables.as<double>();
   s->S.hull = hull ? 1 : 0;
   s->S.full_root = full_root;
   s->S.n_in_nodes = n_in_nodes;
@@ -1001,30 +986,15 @@ RTHX_EXPORT int rthx_scene3d_mirrors(const rthx_scene3d* sc, int64_t* n_mirror, 
 }
 
 RTHX_EXPORT int rthx_trace_exchange_3d(rthx_scene3d* sc, const rthx_trace_args* a, rthx_result* res) {
-  const double t0 = now_ms();
+  rthx::RowTrace rt{now_ms(), a, res};
   if (!sc || !a || !res) return fail(RTHX_EINVAL, "null argument");
-  if (a->bin != 0) return fail(RTHX_EINVAL, "the 3D tracer has one (grey) bin");
-  if (a->n_record != 0) return fail(RTHX_EINVAL, "ray recording is not supported by the 3D tracer");
-  if (a->rays_per_emitter < 0 || a->rays_per_emitter > 0xFFFFFFFFll)
-    return fail(RTHX_ERANGE, "rays_per_emitter must be in [0, 2^32)");
-  if (a->emitter_stride < 1 || a->emitter_begin < 0) return fail(RTHX_EINVAL, "bad emitter range");
-  if (a->device != sc->device) return fail(RTHX_EINVAL, "args.device differs from the scene's device");
-  HIP_TRY(hipSetDevice(sc->device), "hipSetDevice");
-  if (res->device >= 0 && res->device != sc->device) return fail(RTHX_EINVAL, "result bound to another device");
-  {  // (an unread async 2D trace on this result: counted and finished before its buffers go)
-    const int rc0 = rthx::absorb_superseded(res);
-    if (rc0) return rc0;
-  }
-  res->device = sc->device;
-  const int64_t N = sc->n_poly, R = a->rays_per_emitter;
-  const int64_t end = std::min<int64_t>(a->emitter_end, N);
-  const int64_t n_rows = end > a->emitter_begin ? (end - a->emitter_begin + a->emitter_stride - 1) / a->emitter_stride : 0;
-  int64_t split = 1;
-  int64_t split_target = kSplitTargetBlocks;
+  RTHX_TRY(rthx::check_row_args(a, "3D"));
+  int64_t split_target = 0;  // (the driver's default)
   if (const char* e = rthx::knob("RTHX_T3_SPLIT_TARGET")) split_target = std::max<int64_t>(1, std::atoll(e));
-  if (n_rows > 0 && R >= 2 * kSplitMinRays)
-    split = std::max<int64_t>(1, std::min<int64_t>((split_target + n_rows - 1) / n_rows, R / kSplitMinRays));
-  const bool pack16 = (R + split - 1) / split < 65536;
+  const int64_t N = sc->n_poly;
+  RTHX_TRY(rthx::row_trace_plan(rt, sc->dev, "scene", N, split_target));
+  const int64_t R = rt.R;
+  const bool pack16 = (R + rt.split - 1) / rt.split < 65536;
   // A box hull's face records and lattice lines sit in LDS beside the row
   // histogram and the stacks; when they do not fit, the plain walk of the
   // whole scene's BVH (root full_root) traces the scene instead.
@@ -1036,69 +1006,18 @@ RTHX_EXPORT int rthx_trace_exchange_3d(rthx_scene3d* sc, const rthx_trace_args* 
   }
   if (lds_bytes + rthx::kTrace3dStaticLds > rthx::kMaxLdsBytes)
     return fail(RTHX_ERANGE, "N too large for the LDS row histogram and walk stacks of the 3D tracer");
-  if (n_rows * split >= (int64_t(1) << 31)) return fail(RTHX_ERANGE, "too many rows in one call");
-  const int64_t row_cap = std::max<int64_t>(1, std::min<int64_t>(N, R));
-  for (rthx_result* q : res->parts) delete q;
-  res->parts.clear();
-  res->interleaved = false;
-  res->valid = false;
-  res->host_row_off = false;
-  res->host_rec = false;
-  res->rec_g.clear();
-  res->N = N;
-  res->R = R;
-  res->n_rows = n_rows;
-  res->begin = a->emitter_begin;
-  res->stride = a->emitter_stride;
-  res->split = split;
-  res->info = rthx_result_info{};
-  res->info.n_emitters = N;
-  res->info.rows_traced = n_rows;
-  res->info.rays_per_emitter = R;
-  res->info.rays_traced = n_rows * R;
-  res->info.n_devices = 1;
-  res->lb_status.release();
-  res->lb_totals.release();
-  res->lb_epoch = 0;
-  HIP_TRY(res->stage_cols.reserve((size_t)n_rows * row_cap * 4), "hipMalloc stage_cols");
-  HIP_TRY(res->stage_cnt.reserve((size_t)n_rows * row_cap * 4), "hipMalloc stage_cnt");
-  HIP_TRY(res->row_nnz.reserve((size_t)n_rows * 4), "hipMalloc row_nnz");
-  HIP_TRY(res->row_tallied.reserve((size_t)n_rows * 4), "hipMalloc row_tallied");
-  HIP_TRY(res->row_off.reserve((size_t)(n_rows + 1) * 8), "hipMalloc row_off");
-  HIP_TRY(res->totals.reserve(4 * 8), "hipMalloc totals");
-  HIP_TRY(res->dense.reserve((size_t)n_rows * N * 4), "hipMalloc dense rows");
-
-  rthx::TallyParams T{};
-  T.n_emitters = N;
-  T.n_rows = n_rows;
-  T.row_cap = row_cap;
-  T.split = (int32_t)split;
-  T.stage_cols = res->stage_cols.as<uint32_t>();
-  T.stage_cnt = res->stage_cnt.as<uint32_t>();
-  T.row_nnz = res->row_nnz.as<uint32_t>();
-  T.row_tallied = res->row_tallied.as<uint32_t>();
-  T.dense = res->dense.as<uint32_t>();
-  T.R = R;
-  rthx::TraceParams P{};
-  P.R = R;
-  P.g_begin = a->emitter_begin;
-  P.g_stride = a->emitter_stride;
-  P.key0 = (uint32_t)a->seed;
-  P.key1 = (uint32_t)(a->seed >> 32);
-  hipStream_t st = sc->stream;
-  HIP_TRY(hipMemsetAsync(res->totals.p, 0, 32, st), "hipMemset totals");
-  if (n_rows > 0) {
-    HIP_TRY(hipMemsetAsync(T.dense, 0, (size_t)n_rows * N * 4, st), "hipMemset dense rows");
-    HIP_TRY(hipMemsetAsync(T.row_tallied, 0, (size_t)n_rows * 4, st), "hipMemset row_tallied");
-  }
-  HIP_TRY(hipEventRecord(sc->ev[0], st), "hipEventRecord");
-  if (n_rows > 0) {
+  RTHX_TRY(rthx::row_trace_begin(rt));
+  if (rt.n_rows > 0) {
     rthx::Trace3dLaunch L{};
     L.S = sc->scene.as<rthx::DevScene3D>();
-    L.P = P;
-    L.T = T;
+    L.P.R = R;
+    L.P.g_begin = a->emitter_begin;
+    L.P.g_stride = a->emitter_stride;
+    L.P.key0 = (uint32_t)a->seed;
+    L.P.key1 = (uint32_t)(a->seed >> 32);
+    L.T = rt.T;
     L.lds_bytes = lds_bytes;
-    L.stream = st;
+    L.stream = sc->dev.stream;
     L.faithful = (a->flags & RTHX_FLAG_FAITHFUL_SAMPLING) != 0;
     L.pack16 = pack16;
     L.top_choice = sc->top_choice;
@@ -1128,28 +1047,5 @@ RTHX_EXPORT int rthx_trace_exchange_3d(rthx_scene3d* sc, const rthx_trace_args* 
     if (L.ghist) L.lds_bytes = rthx::trace3d_dynamic_lds(0, sc->S.stack, use_hull ? sc->S.n_hull_lines : -1);
     HIP_TRY(rthx::launch_trace3d(L), "trace_exchange_3d_kernel launch");
   }
-  HIP_TRY(hipEventRecord(sc->ev[1], st), "hipEventRecord");
-  int64_t totals[4] = {0, 0, 0, 0};
-  {
-    int rc = rthx::finish_staged(res, T, rthx::kMergeDense, st, sc->ev[2], totals);
-    if (rc) return rc;
-  }
-  float ms_trace = 0.f, ms_pack = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms_trace, sc->ev[0], sc->ev[1]), "hipEventElapsedTime");
-  HIP_TRY(hipEventElapsedTime(&ms_pack, sc->ev[1], sc->ev[2]), "hipEventElapsedTime");
-  if (!(a->flags & RTHX_FLAG_DEVICE_ONLY)) {
-    res->h_row_off.resize(n_rows + 1);
-    HIP_TRY(hipMemcpy(res->h_row_off.data(), res->row_off.p, (n_rows + 1) * 8, hipMemcpyDeviceToHost),
-            "hipMemcpy row_off");
-    res->host_row_off = true;
-  }
-  rthx::take_superseded(res, 0);
-  res->info.nnz = totals[0];
-  res->info.lost_total = totals[1];
-  res->info.lost_max_row = totals[2];
-  res->info.trace_ms = ms_trace;
-  res->info.pack_ms = ms_pack;
-  res->valid = true;
-  res->info.total_ms = now_ms() - t0;
-  return RTHX_OK;
+  return rthx::row_trace_finish(rt);
 }
