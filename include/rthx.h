@@ -847,6 +847,33 @@ void rthx_gasbox_destroy(rthx_gasbox* box);
  *     range's CSR. */
 int rthx_gasbox_trace(rthx_gasbox* box, const rthx_trace_args* args, double beta, int64_t ray_begin,
                       rthx_result* res);
+/* The same trace through a medium whose extinction differs from voxel to
+ * voxel: beta_v[n_beta], n_beta = Nv, one beta = kappa +
+ * sigma_s >= 0 per volume in element order (c_x fastest), a host array that is
+ * read during the call only (one trace per band).  Emission, the draws and
+ * their order are the uniform trace's; the free-path draw gives an optical
+ * depth tau = -ln u, and the ray (csrc/rthx_gasbox_walk.h, shared by the
+ * kernel and the host check) crosses the lattice cell by cell:
+ *   - it starts in the cell of its origin; per axis the next plane is
+ *     lo_a + (c_a + (d_a > 0)) h_a, computed from the integer cell, and
+ *     t_a = (plane - o_a) / d_a (+inf where d_a = 0); t_out = min t_a, the
+ *     lowest axis on a tie; the segment in the cell is max(t_out - t, 0);
+ *   - it is absorbed in voxel c iff tau < tau_acc + beta_c seg (strict), at
+ *     column Ns + c_x + n_x (c_y + n_y c_z); otherwise tau_acc grows by
+ *     beta_c seg and c steps by sign(d) along the axis of t_out;
+ *   - leaving [0, n_a) along axis a it ends on face 2 a + (d_a > 0), at the
+ *     wall cell of its two other indices.
+ * A voxel with beta = 0 is legal and absorbs nothing (its column is exactly
+ * 0); an all-zero field gives the transparent box.  A uniform field sends the
+ * rays of the uniform trace with the same seed and agrees with it except for
+ * rays that end within rounding of a cell boundary.  The result, the flags,
+ * the ray ranges and the staging are as above.
+ *   - Checked before any device call, on top of the checks above: beta_v
+ *     NULL, n_beta != Nv, an entry negative or not finite (RTHX_EINVAL).
+ *   - The field is copied on the box's stream into a buffer the box keeps
+ *     and grows. */
+int rthx_gasbox_trace_field(rthx_gasbox* box, const rthx_trace_args* args, const double* beta_v, int64_t n_beta,
+                            int64_t ray_begin, rthx_result* res);
 
 #ifdef __cplusplus
 }

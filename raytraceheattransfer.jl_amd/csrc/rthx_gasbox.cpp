@@ -1,10 +1,11 @@
 // rthx_gasbox.cpp -- the 3D gas-box exchange tracer's C ABI (include/rthx.h
-// rthx_gasbox_*).  The box is six numbers and a lattice, so the
-// handle holds no geometry on the device beyond the sampling tables; a trace
-// is the dense-row sequence of rthx_rowtrace.h (row split, dense per-row
-// counts, row_compact_kernel, row_scan_kernel, csr_pack_kernel) around its
-// own launch and fills the caller's rthx_result.  Every argument check runs
-// before the first HIP call.
+// rthx_gasbox_*).  The box is six numbers and a lattice,
+// so the handle holds no geometry on the device beyond the sampling tables
+// (and the last per-voxel field traced, rthx_gasbox_trace_field); a trace is
+// the dense-row sequence of rthx_rowtrace.h (row split, dense per-row counts,
+// row_compact_kernel, row_scan_kernel, csr_pack_kernel) around its own launch
+// and fills the caller's rthx_result.  Every argument check runs before the
+// first HIP call.
 #define RTHX_HOST_ONLY_TU 1
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,7 @@
 #include "../../include/rthx.h"
 #include "rthx_common.h"
 #include "rthx_gasbox.h"
+#include "rthx_gasbox_walk.h"
 #include "rthx_rowtrace.h"
 
 using rthx::fail;
@@ -25,6 +27,7 @@ namespace gb = rthx::gasbox;
 struct rthx_gasbox {
   gb::Box B{};
   rthx::RowDevice dev;
+  rthx::DevBuf beta_v;  // the field of the last rthx_gasbox_trace_field (grown, never shrunk)
 };
 
 namespace {
@@ -78,12 +81,14 @@ RTHX_EXPORT int rthx_gasbox_create(const double lo[3], const double hi[3], const
 
 RTHX_EXPORT void rthx_gasbox_destroy(rthx_gasbox* box) { delete box; }
 
-RTHX_EXPORT int rthx_gasbox_trace(rthx_gasbox* box, const rthx_trace_args* a, double beta, int64_t ray_begin,
-                                  rthx_result* res) {
+namespace {
+
+// Both traces.  beta_v == nullptr: the uniform medium `beta`; else the field
+// beta_v[n_beta] (checked by the caller apart from its length, which needs
+// the box).
+int trace(rthx_gasbox* box, const rthx_trace_args* a, double beta, const double* beta_v, int64_t n_beta,
+          int64_t ray_begin, rthx_result* res) {
   rthx::RowTrace rt{now_ms(), a, res};
-  // (the checks of the arguments alone come first: they need no handle)
-  if (!a) return fail(RTHX_EINVAL, "null args");
-  if (!(beta >= 0.0) || !std::isfinite(beta)) return fail(RTHX_EINVAL, "beta must be finite and >= 0");
   RTHX_TRY(rthx::check_row_args(a, "gas-box"));
   if (a->flags & ~(RTHX_FLAG_FAITHFUL_SAMPLING | RTHX_FLAG_DEVICE_ONLY))
     return fail(RTHX_EINVAL, "the gas-box tracer takes RTHX_FLAG_FAITHFUL_SAMPLING and RTHX_FLAG_DEVICE_ONLY only");
@@ -92,6 +97,7 @@ RTHX_EXPORT int rthx_gasbox_trace(rthx_gasbox* box, const rthx_trace_args* a, do
     return fail(RTHX_ERANGE, "ray_begin + rays_per_emitter must be below 2^32");
   if (!box || !res) return fail(RTHX_EINVAL, "null box or result");
   const int64_t N = box->B.n_elements;
+  if (beta_v && n_beta != N - box->B.n_surfaces) return fail(RTHX_EINVAL, "n_beta must be the box's Nv");
   RTHX_TRY(rthx::row_trace_plan(rt, box->dev, "box", N, 0));
   const int64_t R = rt.R;
   if (const char* e = rthx::knob("RTHX_GASBOX_SPLIT"))  // (forces the split)
@@ -107,26 +113,63 @@ RTHX_EXPORT int rthx_gasbox_trace(rthx_gasbox* box, const rthx_trace_args* a, do
   const bool fits = gb::lds_bytes(tally, N) <= rthx::kMaxLdsBytes;
   const char* gh = rthx::knob("RTHX_GASBOX_GHIST");
   if (!fits || (gh && gh[0] == '1') || (!(gh && gh[0] == '0') && part_rays < N)) tally = gb::kGlobal;
-  RTHX_TRY(rthx::row_trace_begin(rt));
-  if (rt.n_rows > 0) {
-    gb::Launch L{};
-    L.B = box->B;
-    L.beta = beta;
-    L.tables = box->dev.tables.as<double>();
-    L.R = R;
-    L.ray_base = ray_begin;
-    L.g_begin = a->emitter_begin;
-    L.g_stride = a->emitter_stride;
-    L.n_rows = rt.n_rows;
-    L.split = (int32_t)rt.split;
-    L.key0 = (uint32_t)a->seed;
-    L.key1 = (uint32_t)(a->seed >> 32);
-    L.dense = rt.T.dense;
-    L.row_tallied = rt.T.row_tallied;
-    L.faithful = (a->flags & RTHX_FLAG_FAITHFUL_SAMPLING) != 0;
-    L.tally = tally;
-    L.stream = box->dev.stream;
-    HIP_TRY(gb::launch(L), "gasbox_trace_kernel launch");
+  const bool field = beta_v && rt.n_rows > 0;
+  if (field) {
+    // (on the handle's stream, ahead of the trace's start event: the call's time, not the kernel's)
+    HIP_TRY(box->beta_v.reserve((size_t)n_beta * 8), "hipMalloc beta field");
+    HIP_TRY(hipMemcpyAsync(box->beta_v.p, beta_v, (size_t)n_beta * 8, hipMemcpyHostToDevice, box->dev.stream),
+            "hipMemcpy beta field");
   }
-  return rthx::row_trace_finish(rt);
+  const auto run = [&]() -> int {
+    RTHX_TRY(rthx::row_trace_begin(rt));
+    if (rt.n_rows > 0) {
+      gb::Launch L{};
+      L.B = box->B;
+      L.beta = beta;
+      L.tables = box->dev.tables.as<double>();
+      L.R = R;
+      L.ray_base = ray_begin;
+      L.g_begin = a->emitter_begin;
+      L.g_stride = a->emitter_stride;
+      L.n_rows = rt.n_rows;
+      L.split = (int32_t)rt.split;
+      L.key0 = (uint32_t)a->seed;
+      L.key1 = (uint32_t)(a->seed >> 32);
+      L.dense = rt.T.dense;
+      L.row_tallied = rt.T.row_tallied;
+      L.faithful = (a->flags & RTHX_FLAG_FAITHFUL_SAMPLING) != 0;
+      L.tally = tally;
+      L.stream = box->dev.stream;
+      if (field)
+        HIP_TRY(gb::launch_field(gb::FieldLaunch{L, box->beta_v.as<double>()}), "gasbox_field_trace_kernel launch");
+      else
+        HIP_TRY(gb::launch(L), "gasbox_trace_kernel launch");
+    }
+    return rthx::row_trace_finish(rt);
+  };
+  const int rc = run();
+  // (the copy may still be reading the caller's array when a later step failed)
+  if (rc != RTHX_OK && field) (void)hipStreamSynchronize(box->dev.stream);
+  return rc;
+}
+
+}  // namespace
+
+RTHX_EXPORT int rthx_gasbox_trace(rthx_gasbox* box, const rthx_trace_args* a, double beta, int64_t ray_begin,
+                                  rthx_result* res) {
+  // (the checks of the arguments alone come first: they need no handle)
+  if (!a) return fail(RTHX_EINVAL, "null args");
+  if (!(beta >= 0.0) || !std::isfinite(beta)) return fail(RTHX_EINVAL, "beta must be finite and >= 0");
+  return trace(box, a, beta, nullptr, 0, ray_begin, res);
+}
+
+RTHX_EXPORT int rthx_gasbox_trace_field(rthx_gasbox* box, const rthx_trace_args* a, const double* beta_v,
+                                        int64_t n_beta, int64_t ray_begin, rthx_result* res) {
+  if (!a) return fail(RTHX_EINVAL, "null args");
+  if (!beta_v) return fail(RTHX_EINVAL, "null beta field");
+  if (n_beta < 1 || n_beta >= (int64_t(1) << 31)) return fail(RTHX_EINVAL, "n_beta must be the box's Nv");
+  for (int64_t v = 0; v < n_beta; ++v)
+    if (!(beta_v[v] >= 0.0) || !std::isfinite(beta_v[v]))
+      return fail(RTHX_EINVAL, "every beta of the field must be finite and >= 0");
+  return trace(box, a, 0.0, beta_v, n_beta, ray_begin, res);
 }

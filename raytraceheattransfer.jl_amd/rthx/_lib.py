@@ -157,6 +157,9 @@ def load(path: Optional[str] = None) -> C.CDLL:
         lib.rthx_gasbox_destroy.argtypes = [C.c_void_p]
         lib.rthx_gasbox_destroy.restype = None
         lib.rthx_gasbox_trace.argtypes = [C.c_void_p, C.POINTER(abi.TraceArgs), C.c_double, C.c_int64, C.c_void_p]
+    if hasattr(lib, "rthx_gasbox_trace_field"):  # (older A/B variant libraries lack it)
+        lib.rthx_gasbox_trace_field.argtypes = [C.c_void_p, C.POINTER(abi.TraceArgs), dp, C.c_int64, C.c_int64,
+                                                C.c_void_p]
     if lib.rthx_abi_version() != abi.RTHX_ABI_VERSION:
         raise RthxError("librthx ABI version mismatch")
     _lib = lib

@@ -343,6 +343,7 @@ EXPORTED_SYMBOLS = (
     "rthx_gasbox_create",
     "rthx_gasbox_destroy",
     "rthx_gasbox_trace",
+    "rthx_gasbox_trace_field",
 )
 
 

@@ -245,9 +245,10 @@ def solve_equilibrium(dom, F=None, device: int = 0, verbose: bool = False, max_i
 
 
 def equilibrium_gasbox(box, device: int = 0, F=None, verbose: bool = False, info: Optional[dict] = None):
-    """The grey GERT solve of a GasBox3D (rthx.gasbox): E, b, coeff and h
-    assembled as equilibrium_grey assembles them (walls eps sigma A T^4, gas
-    4 kappa sigma V T^4, b = 1 - eps / omega), the system solved on the device
+    """The grey GERT solve of a GasBox3D or VoxelGasBox3D (rthx.gasbox): E, b,
+    coeff and h assembled as equilibrium_grey assembles them (walls eps sigma
+    A T^4, gas 4 kappa sigma V T^4, b = 1 - eps / omega; kappa and omega =
+    sigma_s / beta per voxel for a VoxelGasBox3D), the system solved on the device
     from the box's device-resident F_smooth (F: a matrix to use instead).
     Writes T_w, q_w (per surface), T_g, q_g (per volume) and energy_error onto
     the box -- an element with T given keeps it and gets q = emitted -
@@ -257,14 +258,20 @@ def equilibrium_gasbox(box, device: int = 0, F=None, verbose: bool = False, info
     n = ns + nv
     area, vol = box.areas(), box.volume()
     eps, kappa = box.epsilon, box.kappa
-    omega = box.sigma_s / box.beta if box.beta > 0.0 else 0.0
+    if np.ndim(kappa) == 0:
+        omega = box.sigma_s / box.beta if box.beta > 0.0 else 0.0
+        scatters = omega > 1e-6
+    else:  # per voxel (omega = 0 where beta = 0)
+        beta = box.beta
+        omega = np.divide(box.sigma_s, beta, out=np.zeros(nv), where=beta > 0.0)
+        scatters = bool(np.any(omega > 1e-6))
     T_in = np.concatenate([box.T_in_w, box.T_in_g])
     q_in = np.concatenate([box.q_in_w, box.q_in_g])
     Q_known = (T_in < 0.0).astype(int)
-    size = np.concatenate([eps * area, np.full(nv, 4.0 * kappa * vol)])  # emission per sigma T^4
+    size = np.concatenate([eps * area, np.broadcast_to(4.0 * kappa * vol, (nv,))])  # emission per sigma T^4
     E = np.where(Q_known == 0, size * STEFAN_BOLTZMANN * np.where(Q_known == 0, T_in, 0.0) ** 4, 0.0)
     b = np.zeros(n)
-    if omega > 1e-6 or np.sum(eps) < n:
+    if scatters or np.sum(eps) < n:
         b[:ns] = 1.0 - eps
         b[ns:] = omega
     h = np.where(Q_known == 1, q_in, E)

@@ -6,7 +6,10 @@ axis-aligned box of n[0] x n[1] x n[2] uniform cells filled with one grey
 medium (kappa, sigma_s), all six faces walls.  Exchange factors are traced by
 librthx (rthx_gasbox_trace, csrc/rthx_gasbox_kernels.hip); smoothing and the
 grey solve are the ones every other domain uses (rthx_smooth_F_result,
-rthx_solve_grey_smoothed).  No CPU fallback.
+rthx_solve_grey_smoothed).  VoxelGasBox3D is the same box with kappa and
+sigma_s given per voxel: its rays walk the lattice
+(rthx_gasbox_trace_field, csrc/rthx_gasbox_field_kernels.hip).  No CPU
+fallback.
 
 Element order (include/rthx.h): surfaces first, faces f = 2 axis + side (x-,
 x+, y-, y+, z-, z+), on a face of axis a with the other axes p < q cell
@@ -263,3 +266,82 @@ class GasBox3D:
             self.close()
         except Exception:
             pass
+
+
+class VoxelGasBox3D(GasBox3D):
+    """The box with one grey medium per voxel: a flame core, a cooler shell,
+    soot layers.
+
+    kappa and sigma_s are each a scalar, n_volumes values in element order
+    (c_x fastest) or an array of shape (n_x, n_y, n_z) indexed
+    [c_x, c_y, c_z]; both are kept per voxel, in element order, and beta is
+    their sum.  Everything else is GasBox3D's.  Rays are traced by
+    rthx_gasbox_trace_field, which crosses the lattice cell by cell; voxels
+    with beta = 0 are legal in trace() and absorb nothing, but __call__
+    refuses them: a transparent voxel exchanges no heat and would have to
+    leave the system that is smoothed and solved."""
+
+    def __init__(self, lo, hi, n, kappa, sigma_s=0.0, epsilon=1.0, T_in_w=0.0, q_in_w=0.0, T_in_g=-1.0,
+                 q_in_g=0.0):
+        super().__init__(lo, hi, n, 0.0, 0.0, epsilon=epsilon, T_in_w=T_in_w, q_in_w=q_in_w, T_in_g=T_in_g,
+                         q_in_g=q_in_g)
+        self.kappa = self._field(kappa, "kappa")
+        self.sigma_s = self._field(sigma_s, "sigma_s")
+
+    def _field(self, v, name) -> np.ndarray:
+        """A scalar, n_volumes values in element order or an (n_x, n_y, n_z)
+        array -> n_volumes values in element order, finite and >= 0."""
+        a = np.asarray(v, dtype=np.float64)
+        shape = tuple(int(k) for k in self.n)
+        if a.ndim == 0:
+            out = np.full(self.n_volumes, float(a))
+        elif a.ndim == 3 and a.shape == shape:
+            out = a.transpose(2, 1, 0).reshape(-1).copy()  # [c_x, c_y, c_z] -> c_x + n_x (c_y + n_y c_z)
+        elif a.ndim == 1 and a.size == self.n_volumes:
+            out = a.copy()
+        else:
+            raise ValueError(f"{name}: a scalar, {self.n_volumes} volume values in element order or an array of "
+                             f"shape {shape}")
+        if not (np.all(np.isfinite(out)) and np.all(out >= 0.0)):
+            raise ValueError(f"{name} must be finite and >= 0 in every voxel")
+        return out
+
+    @property
+    def beta(self) -> np.ndarray:
+        return self.kappa + self.sigma_s
+
+    def weights(self) -> np.ndarray:
+        """Wall areas, then max(1e-6, 4 beta_v V) per volume (get_w's rule,
+        voxel by voxel)."""
+        return np.concatenate([self.areas(), np.maximum(1e-6, 4.0 * self.beta * self.volume())])
+
+    def trace(self, rays_per_emitter: int, seed: int = 1, faithful: bool = False, ray_begin: int = 0,
+              emitter_begin: int = 0, emitter_end: Optional[int] = None, emitter_stride: int = 1, result=None,
+              device: Optional[int] = None, beta=None):
+        """rthx_gasbox_trace_field into a DeviceResult, as GasBox3D.trace.
+        `beta` overrides the field kappa + sigma_s (a scalar, element order or
+        [c_x, c_y, c_z]; one trace per band)."""
+        from ._lib import DeviceResult, check, load, make_args
+
+        dev = self.device if device is None else int(device)
+        flags = (abi.RTHX_FLAG_FAITHFUL_SAMPLING if faithful else 0) | abi.RTHX_FLAG_DEVICE_ONLY
+        args, _keep = make_args(0, rays_per_emitter, 0.0, seed, emitter_begin,
+                                self.num_elements if emitter_end is None else emitter_end, emitter_stride, dev, flags)
+        field = np.ascontiguousarray(self.beta if beta is None else self._field(beta, "beta"), dtype=np.float64)
+        res = DeviceResult() if result is None else result
+        try:
+            check(load().rthx_gasbox_trace_field(self._handle(dev), C.byref(args), abi.ptr(field, C.c_double),
+                                                 field.size, int(ray_begin), res.handle))
+        except Exception:
+            if result is None:
+                res.close()
+            raise
+        return res
+
+    def __call__(self, rays_tot: int, seed: int = 1, device: int = 0, max_iters: int = 1000, verbose: bool = False,
+                 k_dykstra: Optional[int] = None):
+        if np.any(self.beta == 0.0):
+            raise ValueError("a voxel with beta = 0 takes no part in the exchange: smoothing and the solve need "
+                             "beta > 0 in every voxel (trace() accepts such a field)")
+        return super().__call__(rays_tot, seed=seed, device=device, max_iters=max_iters, verbose=verbose,
+                                k_dykstra=k_dykstra)
