@@ -718,7 +718,11 @@ int rthx_scene3d_create(const double* xyz, const int32_t* nv, const double* norm
  * face cannot be hit by a ray leaving that face at a positive angle, so this
  * only removes round-off hits at t ~ 0 and lets the walk skip the emitter's
  * face.  Each group's polygons must be one contiguous run of indices
- * (face-major sub-face order), else RTHX_EINVAL. */
+ * (face-major sub-face order), else RTHX_EINVAL.  Coplanarity is not
+ * checked: with a group that is not coplanar, a ray whose nearest hit lies in
+ * its emitter's group passes on to what lies behind, or is lost (lost_total)
+ * when nothing does (the BVH walk's counts); such a scene does not take the
+ * convex-enclosure map (rthx_scene3d_hull). */
 int rthx_scene3d_create_grouped(const double* xyz, const int32_t* nv, const double* normal, const int32_t* group,
                                 int64_t n, int32_t device, rthx_scene3d** out);
 void rthx_scene3d_destroy(rthx_scene3d* scene);
@@ -740,8 +744,11 @@ int rthx_scene3d_stats(const rthx_scene3d* scene, int64_t* n_tri, int64_t* n_nod
  * front of every emitting plane, e.g. the readme's icosphere with inward
  * normals): a ray's exit triangle is found from a cube map of exit
  * directions about the centroid (rthx_trace3d.h CvxPlane), again with the
- * same test and counts.  hull_tris / interior_tris: the triangles of each
- * kind (box hull). */
+ * same test and counts.  The map is taken only when every group is coplanar
+ * (every vertex of a group within 1e-12 of the scene scale of its first
+ * polygon's plane): it applies no group skip of its own, and a scene with a
+ * group that is not coplanar walks (*hull = 0).  hull_tris / interior_tris:
+ * the triangles of each kind (box hull). */
 int rthx_scene3d_hull(const rthx_scene3d* scene, int32_t* hull, int64_t* hull_tris, int64_t* interior_tris);
 /* Specular symmetry planes.  As rthx_scene3d_create_grouped
  * (its five first arguments, NULL group included), with n_mirror planar

@@ -578,6 +578,25 @@ bool detect_convex_enclosure(const std::vector<rthx::Emit3>& P, const std::vecto
   return true;
 }
 
+// Does every group of more than one polygon lie in one plane -- each vertex
+// of the group within tol of its first polygon's plane?  The exit-direction
+// map applies no emitter-group skip (Walk::convex_exit): it relies on a
+// ray's own plane never being an exit plane (n . d > 0 there), which covers
+// the emitter's group only when the group is coplanar.
+bool groups_coplanar(const std::vector<rthx::Emit3>& P, double tol) {
+  const int64_t n = (int64_t)P.size();
+  for (int64_t b = 0; b < n; b = P[(size_t)b].ghi) {
+    const rthx::Emit3& E = P[(size_t)b];
+    const V nn{E.n[0], E.n[1], E.n[2]}, p0{E.v[0][0], E.v[0][1], E.v[0][2]};
+    for (int64_t p = b + 1; p < E.ghi; ++p)
+      for (int i = 0; i < P[(size_t)p].nv; ++i) {
+        const V q{P[(size_t)p].v[i][0], P[(size_t)p].v[i][1], P[(size_t)p].v[i][2]};
+        if (!(std::fabs(dot(nn, sub(q, p0))) <= tol)) return false;
+      }
+  }
+  return true;
+}
+
 // Leaf references of `nodes` shifted by `tri_off` triangles and inner
 // references by `node_off` nodes (a BVH appended behind another).
 void shift_bvh(std::vector<rthx::Bvh2Node>& nodes, int32_t node_off, int32_t tri_off) {
@@ -877,10 +896,14 @@ RTHX_EXPORT int rthx_scene3d_create_mirrored(const double* xyz, const int32_t* n
     tris_sorted.swap(all_tris);
   }
   // Convex enclosure seen from inside (no box hull): the cube map of exit
-  // directions (rthx_trace3d.h CvxPlane)
+  // directions (rthx_trace3d.h CvxPlane).  Not with a group that is not
+  // coplanar (within the vertex test's 1e-12 of the scene scale): the map
+  // would count rays that leave through their emitter's group, which the
+  // walk loses.
   CvxBuild cvb;
   const char* no_cvx = rthx::knob("RTHX_T3_NO_CVX");
-  const bool cvx = n_mirror == 0 && !hull && !(no_cvx && no_cvx[0] == '1') && detect_convex_enclosure(polys, tris_sorted, scale, cvb);
+  const bool cvx = n_mirror == 0 && !hull && !(no_cvx && no_cvx[0] == '1') && (!group || groups_coplanar(polys, 1e-12 * scale)) &&
+                   detect_convex_enclosure(polys, tris_sorted, scale, cvb);
 
   const double t_bvh = now_ms();
   RTHX_TRY(rthx::open_device(device, nullptr));  // (the stream: below, once the handle exists)
