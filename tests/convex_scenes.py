@@ -76,7 +76,7 @@ def box(L, nd, rotate=False):
     (u, v the other axes), face-major, so each face is a contiguous coplanar
     group.  `rotate`: turned by rodrigues() about the origin, so that no face
     lies on a plane of the scene's bounding box (a grouped box is then no box
-    hull, rthx_trace3d.cpp detect_box_hull).  Returns (xyz, nv, normals,
+    hull, rthx_scene3d_build.cpp detect_box_hull).  Returns (xyz, nv, normals,
     groups)."""
     lines = [np.linspace(0.0, float(L[k]), int(nd[k]) + 1) for k in range(3)]
     polys, groups = [], []

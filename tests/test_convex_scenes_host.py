@@ -28,7 +28,7 @@ ALL = list(S.CASES) + ["domain_icosphere", "noncoplanar1", "noncoplanar2"]
 
 @pytest.mark.parametrize("name", ALL)
 def test_scene_passes_the_vertex_test(name):
-    """rthx_trace3d.cpp detect_convex_enclosure: every vertex on or in front
+    """rthx_scene3d_build.cpp detect_convex_enclosure: every vertex on or in front
     of every emitting plane within 1e-12 of the scene scale (the largest
     |coordinate| or extent), the centroid more than 1e-6 of it inside, and
     no triangle wider than 1.4 rad from its centre direction to a corner."""
