@@ -734,7 +734,7 @@ int rthx_scene3d_stats(const rthx_scene3d* scene, int64_t* n_tri, int64_t* n_nod
                        int64_t* lds_bytes);
 /* Box hull of a grouped scene (any pointer may be NULL): *hull = 1 when six
  * of its coplanar groups are the faces of its bounding box, each a lattice of
- * quads (rthx_trace3d.h HullFace), 2 when in addition the other (interior)
+ * quads (rthx_scene3d.h HullFace), 2 when in addition the other (interior)
  * triangles form one convex set seen from the sides their rays leave.  Hull
  * hits are then found from the lattice (the same Moeller-Trumbore test on the
  * candidate cells), the BVH walk covers the interior triangles only, and
@@ -743,7 +743,7 @@ int rthx_scene3d_stats(const rthx_scene3d* scene, int64_t* n_tri, int64_t* n_nod
  * scene is one convex enclosure seen from inside (every vertex on or in
  * front of every emitting plane, e.g. the readme's icosphere with inward
  * normals): a ray's exit triangle is found from a cube map of exit
- * directions about the centroid (rthx_trace3d.h CvxPlane), again with the
+ * directions about the centroid (rthx_scene3d.h CvxPlane), again with the
  * same test and counts.  The map is taken only when every group is coplanar
  * (every vertex of a group within 1e-12 of the scene scale of its first
  * polygon's plane): it applies no group skip of its own, and a scene with a

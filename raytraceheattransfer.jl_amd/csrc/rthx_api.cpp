@@ -11,20 +11,19 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/rthx.h"
-#include "rthx_grid.h"
+#include "rthx_domain2d_build.h"
 #include "rthx_kernels.h"
 
 #include "rthx_common.h"
@@ -42,31 +41,6 @@ int fail(int code, const std::string& msg) {
   g_last_error = msg;
   return code;
 }
-
-// Device lookup tables (rthx_device.h): cos/sin(2 pi j/256) for
-// cos_2pi_u32, and for neg_log_tab per entry i the centre c of its z interval
-// [0.6875 + ..), invc = fl(1/c) and ln(invc) split into hi + lo, evaluated in
-// long double.
-void fill_tables(double* t) {
-  for (int j = 0; j < rthx::kCosTable; ++j) {
-    const long double a = 2.0L * 3.141592653589793238462643383279502884L * j / rthx::kCosTable;
-    t[2 * j] = (double)cosl(a);
-    t[2 * j + 1] = (double)sinl(a);
-  }
-  double* L = t + rthx::kLogTableOffset;
-  for (int i = 0; i < rthx::kLogTable; ++i) {
-    const double z0 = rthx::bitsd(rthx::kLogOff + ((uint64_t)i << 45));
-    const double z1 = rthx::bitsd(rthx::kLogOff + ((uint64_t)(i + 1) << 45));
-    const double invc = (double)(2.0L / ((long double)z0 + (long double)z1));
-    const long double T = logl((long double)invc);
-    const double hi = (double)T;
-    L[4 * i] = invc;
-    L[4 * i + 1] = hi;
-    L[4 * i + 2] = (double)(T - (long double)hi);
-    L[4 * i + 3] = 0.0;
-  }
-}
-
 
 namespace {
 hipError_t lib_stream(int device, hipStream_t* out, int which) {
@@ -145,22 +119,6 @@ int upload(rthx_domain* d, const T* src, size_t n, const T** dst, const char* wh
   return RTHX_OK;
 }
 
-int check_grid(const rthx_grid_desc& g, int32_t count, const char* what) {
-  if (g.nx < 1 || g.ny < 1 || !g.cell_start || !(std::isfinite(g.inv_cell_size)) || g.inv_cell_size <= 0)
-    return fail(RTHX_EINVAL, std::string("invalid grid: ") + what);
-  int64_t cells = (int64_t)g.nx * g.ny;
-  if (cells > (1ll << 30)) return fail(RTHX_ERANGE, std::string("grid too large: ") + what);
-  if (g.cell_start[0] != 0) return fail(RTHX_EINVAL, std::string("grid cell_start[0] != 0: ") + what);
-  for (int64_t c = 0; c < cells; ++c)
-    if (g.cell_start[c + 1] < g.cell_start[c]) return fail(RTHX_EINVAL, std::string("grid cell_start not monotone: ") + what);
-  int64_t n_items = g.cell_start[cells];
-  if (n_items > 0 && !g.cell_items) return fail(RTHX_EINVAL, std::string("null grid items: ") + what);
-  for (int64_t k = 0; k < n_items; ++k)
-    if (g.cell_items[k] < 0 || g.cell_items[k] >= count)
-      return fail(RTHX_EINVAL, std::string("grid item out of range: ") + what);
-  return RTHX_OK;
-}
-
 // Row splitting.  A launch of fewer rows than half the chip's resident
 // workgroup slots (CUs x workgroups per CU of the unsplit kernel, from the
 // occupancy query) leaves CUs idle for the whole trace, so every row is
@@ -174,24 +132,6 @@ int check_grid(const rthx_grid_desc& g, int32_t count, const char* what) {
 // RTHX_SPLIT_TARGET=<workgroups> replaces the slot count and
 // RTHX_SPLIT_BELOW=<rows> splits only launches of fewer rows (1: never).
 constexpr int64_t kSplitMinRays = 2048;
-
-// Device point-location grids: rthx_grid.cpp.  Cells per mean polygon extent
-// (per axis): at 2 a cell holds at most one vertex of a regular mesh.
-constexpr double kGridCellsPerPolygon = 2.0;
-
-rthx::DevGrid add_grid(const int32_t* nv, const double* xy, int first, int count,
-                       std::vector<rthx::CellRec>& cells, std::vector<int32_t>& lists, std::vector<int32_t>& items) {
-  rthx::DevGrid g{};
-  g.cell_base = (int32_t)cells.size();
-  rthx::GridBuild b = rthx::build_cell_grid(nv, xy, first, count, kGridCellsPerPolygon, cells, lists, items);
-  g.ox = b.ox;
-  g.oy = b.oy;
-  g.inv_x = b.inv_x;
-  g.inv_y = b.inv_y;
-  g.nx = b.nx;
-  g.ny = b.ny;
-  return g;
-}
 
 }  // namespace
 
@@ -310,456 +250,109 @@ RTHX_EXPORT int rthx_device_synchronize(int32_t device) {
   return RTHX_OK;
 }
 
+// The host work -- the descriptor's checks, the derived arrays, the grids, the
+// tables and the choice and layout of the fast paths -- is build_domain2d
+// (rthx_domain2d_build.h); here the knobs are read and the result is uploaded.
 RTHX_EXPORT int rthx_domain_create(const rthx_domain_desc* desc, int32_t device, rthx_domain** out) {
   if (!out) return fail(RTHX_EINVAL, "null out");
   *out = nullptr;
   if (!desc) return fail(RTHX_EINVAL, "null descriptor");
   if (desc->abi_version != RTHX_ABI_VERSION) return fail(RTHX_EINVAL, "descriptor ABI version mismatch");
   const rthx_domain_desc& s = *desc;
-  if (s.n_coarse < 1 || s.n_fine < 1 || s.n_surfaces < 0 || s.n_bins < 1)
-    return fail(RTHX_EINVAL, "empty or negative domain sizes");
-  if ((int64_t)s.n_surfaces + s.n_fine >= (1ll << 31)) return fail(RTHX_ERANGE, "too many elements");
-  if (!s.coarse_nv || !s.coarse_xy || !s.coarse_normal || !s.coarse_solid || !s.coarse_bbox || !s.fine_offset ||
-      !s.fine_nv || !s.fine_xy || !s.fine_normal || !s.fine_mid || !s.fine_volume || !s.fine_bbox ||
-      !s.fine_surface || !s.fine_grid || !s.beta || !s.uniform_beta)
-    return fail(RTHX_EINVAL, "null descriptor array");
-  for (int c = 0; c < s.n_coarse; ++c)
-    if (s.coarse_nv[c] != 3 && s.coarse_nv[c] != 4) return fail(RTHX_EINVAL, "coarse polygon with n not in {3,4}");
-  if (s.fine_offset[0] != 0 || s.fine_offset[s.n_coarse] != s.n_fine)
-    return fail(RTHX_EINVAL, "fine_offset must run from 0 to n_fine");
-  for (int c = 0; c < s.n_coarse; ++c)
-    if (s.fine_offset[c + 1] <= s.fine_offset[c]) return fail(RTHX_EINVAL, "coarse polygon without fine polygons");
-  for (int f = 0; f < s.n_fine; ++f)
-    if (s.fine_nv[f] != 3 && s.fine_nv[f] != 4) return fail(RTHX_EINVAL, "fine polygon with n not in {3,4}");
-  std::vector<int32_t> s_face(s.n_surfaces, -1), s_wall(s.n_surfaces, -1);
-  for (int f = 0; f < s.n_fine; ++f)
-    for (int w = 0; w < 4; ++w) {
-      int32_t sidx = s.fine_surface[4 * (size_t)f + w];
-      if (sidx < -1 || sidx >= s.n_surfaces || (sidx >= 0 && w >= s.fine_nv[f]))
-        return fail(RTHX_EINVAL, "fine_surface index out of range");
-      if (sidx >= 0) {
-        if (s_face[sidx] != -1) return fail(RTHX_EINVAL, "surface index used twice");
-        s_face[sidx] = f;
-        s_wall[sidx] = w;
-      }
-    }
-  for (int i = 0; i < s.n_surfaces; ++i)
-    if (s_face[i] < 0) return fail(RTHX_EINVAL, "surface index without a solid fine wall");
-  for (int64_t k = 0; k < (int64_t)s.n_bins * s.n_fine; ++k)
-    if (!std::isfinite(s.beta[k]) || s.beta[k] < 0) return fail(RTHX_EINVAL, "non-finite or negative extinction");
-  for (int64_t k = 0; k < 8ll * s.n_fine; ++k)
-    if (!std::isfinite(s.fine_xy[k]) || !std::isfinite(s.fine_normal[k]))
-      return fail(RTHX_EINVAL, "non-finite fine geometry");
-  int rc = check_grid(s.coarse_grid, s.n_coarse, "coarse grid");
-  if (rc) return rc;
-  for (int c = 0; c < s.n_coarse; ++c) {
-    rc = check_grid(s.fine_grid[c], s.fine_offset[c + 1] - s.fine_offset[c], "fine grid");
-    if (rc) return rc;
-  }
+  rthx::Domain2dOptions opt;
+  opt.no_mlat = env_flag("RTHX_NO_MLAT");
+  opt.no_lat = env_flag("RTHX_NO_LAT");
+  // RTHX_LAT_GUESS_SCALE (tests): the first guess of the LAT cell scaled.  The
+  // guess only seeds the exact search against xs / ys, so the counts are the
+  // same for any scale; a scale off 1 sends most rays through the LAT ray's
+  // fix-up block (rthx_device.h lat_ray_fixup).
+  if (const char* gs = rthx::knob("RTHX_LAT_GUESS_SCALE")) opt.lat_guess_scale = std::strtod(gs, nullptr);
+  rthx::Domain2dBuild B;
+  std::string err;
+  if (const int rc = rthx::build_domain2d(s, opt, B, err)) return fail(rc, err);
 
   RTHX_TRY(rthx::open_device(device, nullptr));  // (the stream: below, once the handle exists)
-
-  rthx_domain* d = new (std::nothrow) rthx_domain();
+  std::unique_ptr<rthx_domain> d(new (std::nothrow) rthx_domain());
   if (!d) return fail(RTHX_ENOMEM, "host allocation failed");
   d->device = device;
-  d->n_emitters = (int64_t)s.n_surfaces + s.n_fine;
-  d->n_bins = s.n_bins;
-  d->uniform_beta.assign(s.uniform_beta, s.uniform_beta + s.n_bins);
-  d->beta_first.resize(s.n_bins);
-  for (int b = 0; b < s.n_bins; ++b) d->beta_first[b] = s.beta[(size_t)b * s.n_fine];
-
-  auto bail = [&](int code) {
-    delete d;
-    return code;
-  };
-  if (rthx::device_stream(device, &d->stream) != hipSuccess) return bail(fail(RTHX_EDEVICE, "hipStreamCreate"));
+  if (rthx::device_stream(device, &d->stream) != hipSuccess) return fail(RTHX_EDEVICE, "hipStreamCreate");
   for (auto& e : d->ev)
-    if (hipEventCreate(&e) != hipSuccess) return bail(fail(RTHX_EDEVICE, "hipEventCreate"));
+    if (hipEventCreate(&e) != hipSuccess) return fail(RTHX_EDEVICE, "hipEventCreate");
 
   rthx::DevDomain& D = d->D;
+  const size_t nc = s.n_coarse, nf = s.n_fine;
+  const std::vector<uint32_t> no_mirror(nc, 0u);  // (until rthx_domain_set_mirror_walls flags some)
+  int rc = RTHX_OK;
+  auto up = [&](const auto* src, size_t n, auto& dst, const char* what) {
+    if (rc == RTHX_OK) rc = upload(d.get(), src, n, &dst, what);
+  };
+  auto up_blob = [&](const std::vector<unsigned char>& b, const uint4*& dst, const char* what) {
+    up(reinterpret_cast<const uint4*>(b.data()), b.size() / 16, dst, what);
+  };
+  up(B.cpoly.data(), nc, D.c_poly, "D.c_poly");
+  up(B.csolid.data(), nc, D.c_solid, "D.c_solid");
+  up(no_mirror.data(), nc, D.c_mirror, "D.c_mirror");
+  up(s.coarse_bbox, 4 * nc, D.c_bbox, "D.c_bbox");
+  up(s.fine_offset, nc + 1, D.f_offset, "D.f_offset");
+  up(s.fine_nv, nf, D.f_nv, "D.f_nv");
+  up(B.fpoly.data(), nf, D.f_poly, "D.f_poly");
+  up(s.fine_mid, 2 * nf, D.f_mid, "D.f_mid");
+  up(B.trifrac.data(), nf, D.f_trifrac, "D.f_trifrac");
+  up(s.fine_bbox, 4 * nf, D.f_bbox, "D.f_bbox");
+  up(s.fine_surface, 4 * nf, D.f_surf, "D.f_surf");
+  up(B.fcoarse.data(), nf, D.f_coarse, "D.f_coarse");
+  up(B.fgrids.data(), nc, D.f_grid, "D.f_grid");
+  up(reinterpret_cast<const rthx::DevCell*>(B.gcells.data()), B.gcells.size(), D.grid_cells, "D.grid_cells");
+  up(B.glists.data(), B.glists.size(), D.grid_lists, "D.grid_lists");
+  up(B.gitems.data(), B.gitems.size(), D.grid_items, "D.grid_items");
+  up(s.beta, (size_t)s.n_bins * nf, D.beta, "D.beta");
+  up(B.s_face.data(), B.s_face.size(), D.s_face, "D.s_face");
+  up(B.s_wall.data(), B.s_wall.size(), D.s_wall, "D.s_wall");
+  up(B.tables.data(), B.tables.size(), D.tables, "D.tables");
+  // (what a fast path does not use is empty and stays a null pointer)
+  up_blob(B.c_blob, D.c_blob, "D.c_blob");
+  up(B.c_beta.data(), B.c_beta.size(), D.c_beta, "D.c_beta");
+  up_blob(B.ml_blob, D.ml_blob, "D.ml_blob");
+  up(B.ml_bbeta.data(), B.ml_bbeta.size(), D.ml_bbeta, "D.ml_bbeta");
+  up_blob(B.lat_blob, D.lat_blob, "D.lat_blob");
+  up(B.lat_map.data(), B.lat_map.size(), D.lat_map, "D.lat_map");
   D.n_coarse = s.n_coarse;
   D.n_fine = s.n_fine;
   D.n_surfaces = s.n_surfaces;
   D.n_bins = s.n_bins;
-  std::vector<uint32_t> csolid(s.n_coarse, 0u);
-  for (int c = 0; c < s.n_coarse; ++c)
-    for (int w = 0; w < 4; ++w)
-      if (s.coarse_solid[4 * c + w]) csolid[c] |= 1u << w;
-  // area(ABC)/V of every quad (emitVolumeRay2D.jl:7), evaluated exactly as the
-  // reference's expression (no contraction: -ffp-contract=off)
-  std::vector<double> trifrac(s.n_fine, 0.0);
-  for (int f = 0; f < s.n_fine; ++f) {
-    if (s.fine_nv[f] != 4) continue;
-    const double* v = s.fine_xy + 8 * (size_t)f;
-    trifrac[f] = 0.5 * (v[0] * (v[3] - v[5]) + v[2] * (v[5] - v[1]) + v[4] * (v[1] - v[3])) / s.fine_volume[f];
-  }
-  // one convex coarse polygon -> SINGLE kernels (a ray that leaves it is lost)
-  if (s.n_coarse == 1) {
-    const double* v = s.coarse_xy;
-    int n = s.coarse_nv[0], pos = 0, neg = 0;
-    for (int i = 0; i < n; ++i) {
-      int j = (i + 1) % n, k = (i + 2) % n;
-      double cr = (v[2 * j] - v[2 * i]) * (v[2 * k + 1] - v[2 * j + 1]) - (v[2 * j + 1] - v[2 * i + 1]) * (v[2 * k] - v[2 * j]);
-      pos += cr > 0;
-      neg += cr < 0;
-    }
-    d->single_convex = (pos == 0 || neg == 0);
-  }
-  std::vector<int32_t> fcoarse(s.n_fine);
-  for (int c = 0; c < s.n_coarse; ++c)
-    for (int f = s.fine_offset[c]; f < s.fine_offset[c + 1]; ++f) fcoarse[f] = c;
+  D.c_grid = B.c_grid;
+  D.cl = B.cl;
+  D.ml = B.ml;
+  D.lat = B.lat;
+  up(&d->D, 1, d->d_dom, "domain record");
+  if (rc) return rc;
 
-  // device point-location grids: coarse first, then one per coarse polygon
-  std::vector<rthx::CellRec> gcells;
-  std::vector<int32_t> glists, gitems;
-  D.c_grid = add_grid(s.coarse_nv, s.coarse_xy, 0, s.n_coarse, gcells, glists, gitems);
-  std::vector<rthx::DevGrid> fgrids(s.n_coarse);
-  for (int c = 0; c < s.n_coarse; ++c)
-    fgrids[c] = add_grid(s.fine_nv, s.fine_xy, s.fine_offset[c], s.fine_offset[c + 1] - s.fine_offset[c], gcells,
-                         glists, gitems);
-  if (gcells.size() >= (1ull << 30) || gitems.size() >= (1ull << 31)) return bail(fail(RTHX_ERANGE, "grids too large"));
-  if (gitems.empty()) gitems.push_back(0);
-
-  const size_t nc = s.n_coarse, nf = s.n_fine;
-#define UP(src, n, dst)                                          \
-  do {                                                           \
-    int _r = upload(d, (src), (n), &(dst), #dst);                \
-    if (_r) return bail(_r);                                     \
-  } while (0)
-  // polygon records padded to 4 slots (rthx_device.h DevPoly): a triangle
-  // repeats vertex 2 and has a zero normal in slot 3
-  auto polys = [](const int32_t* nv, const double* xy, const double* nrm, size_t n) {
-    std::vector<rthx::DevPoly> out(n);
-    for (size_t p = 0; p < n; ++p) {
-      rthx::DevPoly& q = out[p];
-      for (int i = 0; i < 4; ++i) {
-        const int v = i < nv[p] ? i : nv[p] - 1;
-        q.x[i] = xy[8 * p + 2 * v];
-        q.y[i] = xy[8 * p + 2 * v + 1];
-        q.nx[i] = i < nv[p] ? nrm[8 * p + 2 * i] : 0.0;
-        q.ny[i] = i < nv[p] ? nrm[8 * p + 2 * i + 1] : 0.0;
-      }
-    }
-    return out;
-  };
-  const std::vector<rthx::DevPoly> cpoly = polys(s.coarse_nv, s.coarse_xy, s.coarse_normal, nc);
-  const std::vector<rthx::DevPoly> fpoly = polys(s.fine_nv, s.fine_xy, s.fine_normal, nf);
-  // AXIS kernels (rthx_device.h dist_to_rect): v0 the min corner, CCW, wall
-  // normals exactly (0,-1), (1,0), (0,1), (-1,0) (calculateInwardNormal's
-  // orientation)
-  auto canonical_rect = [](const int32_t nv, const rthx::DevPoly& q) {
-    return nv == 4 && q.x[0] < q.x[1] && q.y[0] < q.y[2] && q.x[1] == q.x[2] && q.x[3] == q.x[0] &&
-           q.y[1] == q.y[0] && q.y[3] == q.y[2] && q.nx[0] == 0.0 && q.ny[0] == -1.0 && q.nx[1] == 1.0 &&
-           q.ny[1] == 0.0 && q.nx[2] == 0.0 && q.ny[2] == 1.0 && q.nx[3] == -1.0 && q.ny[3] == 0.0;
-  };
-  d->axis_rect = true;
-  for (size_t c = 0; c < nc && d->axis_rect; ++c) d->axis_rect = canonical_rect(s.coarse_nv[c], cpoly[c]);
-  for (size_t f = 0; f < nf && d->axis_rect; ++f) d->axis_rect = canonical_rect(s.fine_nv[f], fpoly[f]);
-  // (cos, sin)(2 pi j / 256) for the emission azimuth (cos_2pi_u32) and the
-  // free-path log table (neg_log_tab)
-  // One copy per bin, each followed by the bin's 1 / beta_uniform (the
-  // kernels' kTabInvBeta slot; +inf when beta_uniform <= 0), so that a
-  // kernel reading the tables from global memory finds a whole
-  // kLdsTableDoubles block at bin * kLdsTableDoubles.
-  std::vector<double> tables((size_t)s.n_bins * rthx::kLdsTableDoubles);
-  for (int b = 0; b < s.n_bins; ++b) {
-    double* t = tables.data() + (size_t)b * rthx::kLdsTableDoubles;
-    rthx::fill_tables(t);
-    t[rthx::kTabInvBeta] = d->beta_first[b] > 0 ? 1.0 / d->beta_first[b] : HUGE_VAL;
-  }
-  UP(cpoly.data(), nc, D.c_poly);
-  UP(csolid.data(), nc, D.c_solid);
-  {  // no mirror walls until rthx_domain_set_mirror_walls flags some
-    const std::vector<uint32_t> none(nc, 0u);
-    UP(none.data(), nc, D.c_mirror);
-    d->d_mirror = const_cast<uint32_t*>(static_cast<const uint32_t*>(D.c_mirror));
-    d->c_nv.assign(s.coarse_nv, s.coarse_nv + nc);
-    d->c_xy.assign(s.coarse_xy, s.coarse_xy + 8 * nc);
-    d->c_solid = csolid;
-  }
-  UP(s.coarse_bbox, 4 * nc, D.c_bbox);
-  UP(s.fine_offset, nc + 1, D.f_offset);
-  UP(s.fine_nv, nf, D.f_nv);
-  UP(fpoly.data(), nf, D.f_poly);
-  UP(s.fine_mid, 2 * nf, D.f_mid);
-  UP(trifrac.data(), nf, D.f_trifrac);
-  UP(s.fine_bbox, 4 * nf, D.f_bbox);
-  UP(s.fine_surface, 4 * nf, D.f_surf);
-  UP(fcoarse.data(), nf, D.f_coarse);
-  UP(fgrids.data(), nc, D.f_grid);
-  UP(reinterpret_cast<const rthx::DevCell*>(gcells.data()), gcells.size(), D.grid_cells);
-  UP(glists.data(), glists.size(), D.grid_lists);
-  UP(gitems.data(), gitems.size(), D.grid_items);
-  UP(s.beta, (size_t)s.n_bins * nf, D.beta);
-  UP(s_face.data(), s_face.size(), D.s_face);
-  UP(s_wall.data(), s_wall.size(), D.s_wall);
-  UP(tables.data(), tables.size(), D.tables);
-  // Coarse mesh as the CLDS kernels stage it in LDS (rthx_device.h
-  // CoarseLayout), and per bin the beta every fine polygon of a coarse
-  // polygon shares (-1 when they differ).
-  {
-    const size_t ncells = (size_t)D.c_grid.nx * D.c_grid.ny;
-    auto a16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    rthx::CoarseLayout L{};
-    size_t off = a16(nc * sizeof(rthx::DevPoly));
-    L.off_fgrid = (int32_t)off;
-    off = a16(off + nc * sizeof(rthx::DevGrid));
-    L.off_bbox = (int32_t)off;
-    off = a16(off + nc * 4 * sizeof(double));
-    L.off_first = (int32_t)off;
-    off = a16(off + (nc + 1) * sizeof(int32_t));
-    L.off_solid = (int32_t)off;
-    off = a16(off + nc * sizeof(uint32_t));
-    L.off_cells = (int32_t)off;
-    off = a16(off + ncells * sizeof(rthx::CellRec));
-    L.off_beta = (int32_t)off;
-    L.blob_bytes = (int32_t)off;
-    off = a16(off + nc * sizeof(double));
-    if (nc >= 2 && D.c_grid.cell_base == 0 && off <= rthx::kMaxCoarseLdsBytes) {
-      L.bytes = (int32_t)off;
-      std::vector<uint4> blob((size_t)L.blob_bytes / 16);
-      char* b = reinterpret_cast<char*>(blob.data());
-      std::memset(b, 0, (size_t)L.blob_bytes);
-      std::memcpy(b, cpoly.data(), nc * sizeof(rthx::DevPoly));
-      std::memcpy(b + L.off_fgrid, fgrids.data(), nc * sizeof(rthx::DevGrid));
-      std::memcpy(b + L.off_bbox, s.coarse_bbox, nc * 4 * sizeof(double));
-      std::memcpy(b + L.off_first, s.fine_offset, (nc + 1) * sizeof(int32_t));
-      std::memcpy(b + L.off_solid, csolid.data(), nc * sizeof(uint32_t));
-      std::memcpy(b + L.off_cells, gcells.data(), ncells * sizeof(rthx::CellRec));
-      UP(blob.data(), blob.size(), D.c_blob);
-    }
-    D.cl = L;
-  }
-  std::vector<double> cbeta_all;  // (per bin, per coarse polygon; MLAT reorders it by box)
-  if (nc >= 2) {
-    std::vector<double> cbeta((size_t)s.n_bins * nc, -1.0);
-    for (int bn = 0; bn < s.n_bins; ++bn)
-      for (size_t c = 0; c < nc; ++c) {
-        const int f0 = s.fine_offset[c], f1 = s.fine_offset[c + 1];
-        const double* bb = s.beta + (size_t)bn * nf;
-        bool same = true;
-        for (int f = f0 + 1; f < f1 && same; ++f) same = bb[f] == bb[f0];
-        if (same) cbeta[(size_t)bn * nc + c] = bb[f0];
-      }
-    UP(cbeta.data(), cbeta.size(), D.c_beta);
-    cbeta_all = cbeta;
-  }
-  // Multi-polygon lattice (rthx_device.h MLatLayout; MLAT kernels): the
-  // coarse rectangles are the boxes of a coarse lattice, and the fine
-  // rectangles of each are, x fastest, the boxes of one global fine lattice
-  // inside it.
-  if (!d->single_convex && d->axis_rect && nc >= 2 && !env_flag("RTHX_NO_MLAT")) {
-    auto lines = [](const std::vector<rthx::DevPoly>& q, size_t n, bool xdir) {
-      std::vector<double> v;
-      for (size_t p = 0; p < n; ++p) {
-        v.push_back(xdir ? q[p].x[0] : q[p].y[0]);
-        v.push_back(xdir ? q[p].x[1] : q[p].y[2]);
-      }
-      std::sort(v.begin(), v.end());
-      v.erase(std::unique(v.begin(), v.end()), v.end());
-      return v;
-    };
-    const std::vector<double> xs = lines(fpoly, nf, true), ys = lines(fpoly, nf, false);
-    const std::vector<double> cxs = lines(cpoly, nc, true), cys = lines(cpoly, nc, false);
-    const int64_t nx = (int64_t)xs.size() - 1, ny = (int64_t)ys.size() - 1;
-    const int64_t ncx = (int64_t)cxs.size() - 1, ncy = (int64_t)cys.size() - 1;
-    auto index_of = [](const std::vector<double>& v, double x) -> int64_t {
-      const auto it = std::lower_bound(v.begin(), v.end(), x);
-      return (it != v.end() && *it == x) ? (int64_t)(it - v.begin()) : -1;
-    };
-    bool ok = ncx >= 1 && ncy >= 1 && ncx * ncy == (int64_t)nc && nx <= 65536 && ny <= 65536;
-    std::vector<int32_t> cmap(ok ? (size_t)(ncx * ncy) : 0, -1);
-    std::vector<rthx::MCoarse> info(nc);
-    for (size_t c = 0; c < nc && ok; ++c) {
-      const rthx::DevPoly& q = cpoly[c];
-      const int64_t ci = index_of(cxs, q.x[0]), cj = index_of(cys, q.y[0]);
-      ok = ci >= 0 && cj >= 0 && ci < ncx && cj < ncy && cxs[ci + 1] == q.x[1] && cys[cj + 1] == q.y[2] &&
-           cmap[cj * ncx + ci] < 0;
-      if (!ok) break;
-      cmap[cj * ncx + ci] = (int32_t)c;
-      const int64_t i0 = index_of(xs, q.x[0]), i1 = index_of(xs, q.x[1]);
-      const int64_t j0 = index_of(ys, q.y[0]), j1 = index_of(ys, q.y[2]);
-      const int f0 = s.fine_offset[c], f1 = s.fine_offset[c + 1];
-      ok = i0 >= 0 && i1 > i0 && j0 >= 0 && j1 > j0 && (i1 - i0) * (j1 - j0) == f1 - f0;
-      for (int f = f0; f < f1 && ok; ++f) {
-        const int64_t i = i0 + (f - f0) % (i1 - i0), j = j0 + (f - f0) / (i1 - i0);
-        ok = fpoly[f].x[0] == xs[i] && fpoly[f].x[1] == xs[i + 1] && fpoly[f].y[0] == ys[j] && fpoly[f].y[2] == ys[j + 1];
-      }
-      info[c] = rthx::MCoarse{f0, (int32_t)i0, (int32_t)j0, (int32_t)(i1 - i0), (int32_t)(j1 - j0), (int32_t)ci,
-                              (int32_t)cj, csolid[c]};
-    }
-    if (ok) {
-      auto a16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-      rthx::MLatLayout G{};
-      G.nx = (int32_t)nx;
-      G.ny = (int32_t)ny;
-      G.ncx = (int32_t)ncx;
-      G.ncy = (int32_t)ncy;
-      size_t off = a16(8 * xs.size());
-      G.off_ys = (int32_t)off;
-      off = a16(off + 8 * ys.size());
-      G.off_cxs = (int32_t)off;
-      off = a16(off + 8 * cxs.size());
-      G.off_cys = (int32_t)off;
-      off = a16(off + 8 * cys.size());
-      G.off_cmap = (int32_t)off;
-      off = a16(off + 4 * cmap.size());
-      G.off_cinfo = (int32_t)off;
-      off = a16(off + sizeof(rthx::MCoarse) * nc);
-      G.off_bsolid = (int32_t)off;
-      off = a16(off + 4 * nc);
-      G.off_beta = (int32_t)off;
-      G.blob_bytes = (int32_t)off;
-      off = a16(off + 8 * nc);
-      if (ncx == 1) {  // layer records (walk_layers), staged per bin
-        G.off_lay = (int32_t)off;
-        off = a16(off + sizeof(rthx::LayerRec) * (size_t)(ncy + 2));  // (sentinels below and above)
-      }
-      G.inv_x = (double)nx / (xs[nx] - xs[0]);
-      G.inv_y = (double)ny / (ys[ny] - ys[0]);
-      G.inv_cx = (double)ncx / (cxs[ncx] - cxs[0]);
-      G.inv_cy = (double)ncy / (cys[ncy] - cys[0]);
-      if (off <= rthx::kMaxCoarseLdsBytes) {
-        G.bytes = (int32_t)off;
-        std::vector<uint4> blob((size_t)G.blob_bytes / 16);
-        char* b = reinterpret_cast<char*>(blob.data());
-        std::memset(b, 0, (size_t)G.blob_bytes);
-        std::memcpy(b, xs.data(), 8 * xs.size());
-        std::memcpy(b + G.off_ys, ys.data(), 8 * ys.size());
-        std::memcpy(b + G.off_cxs, cxs.data(), 8 * cxs.size());
-        std::memcpy(b + G.off_cys, cys.data(), 8 * cys.size());
-        std::memcpy(b + G.off_cmap, cmap.data(), 4 * cmap.size());
-        std::memcpy(b + G.off_cinfo, info.data(), sizeof(rthx::MCoarse) * nc);
-        std::vector<uint32_t> bsolid(nc);
-        std::vector<double> bbeta((size_t)s.n_bins * nc);
-        for (size_t bx = 0; bx < nc; ++bx) {
-          const int c = cmap[bx];
-          bsolid[bx] = csolid[c];
-          for (int bn = 0; bn < s.n_bins; ++bn) bbeta[(size_t)bn * nc + bx] = cbeta_all[(size_t)bn * nc + c];
-        }
-        std::memcpy(b + G.off_bsolid, bsolid.data(), 4 * nc);
-        UP(blob.data(), blob.size(), D.ml_blob);
-        UP(bbeta.data(), bbeta.size(), D.ml_bbeta);
-        d->ml_mixed.assign((size_t)s.n_bins, 0);
-        for (int bn = 0; bn < s.n_bins; ++bn)
-          for (size_t bx = 0; bx < nc; ++bx) d->ml_mixed[bn] |= bbeta[(size_t)bn * nc + bx] < 0.0 ? 1 : 0;
-        D.ml = G;
-      }
-    }
-  }
-  // Lattice of a single axis-aligned coarse rectangle (rthx_device.h
-  // LatticeLayout; LAT kernels): the fine cells must be exactly the nx x ny
-  // boxes between the sorted distinct x and y coordinates, and only boundary
-  // fine walls may be solid.
-  if (d->single_convex && d->axis_rect && !env_flag("RTHX_NO_LAT")) {
-    std::vector<double> xs, ys;
-    for (size_t f = 0; f < nf; ++f) {
-      xs.push_back(fpoly[f].x[0]);
-      xs.push_back(fpoly[f].x[1]);
-      ys.push_back(fpoly[f].y[0]);
-      ys.push_back(fpoly[f].y[2]);
-    }
-    std::sort(xs.begin(), xs.end());
-    xs.erase(std::unique(xs.begin(), xs.end()), xs.end());
-    std::sort(ys.begin(), ys.end());
-    ys.erase(std::unique(ys.begin(), ys.end()), ys.end());
-    const int64_t lnx = (int64_t)xs.size() - 1, lny = (int64_t)ys.size() - 1;
-    bool ok = lnx >= 1 && lny >= 1 && lnx * lny == (int64_t)nf && lnx <= rthx::kLatMaxDim && lny <= rthx::kLatMaxDim;  // (lat_cell: 24-bit products)
-    std::vector<int32_t> map(ok ? (size_t)(lnx * lny) : 0, -1);
-    bool identity = ok;
-    for (size_t f = 0; f < nf && ok; ++f) {
-      const auto ix = std::lower_bound(xs.begin(), xs.end(), fpoly[f].x[0]) - xs.begin();
-      const auto iy = std::lower_bound(ys.begin(), ys.end(), fpoly[f].y[0]) - ys.begin();
-      ok = ix < lnx && iy < lny && xs[ix + 1] == fpoly[f].x[1] && ys[iy + 1] == fpoly[f].y[2] &&
-           map[iy * lnx + ix] < 0;
-      if (!ok) break;
-      map[iy * lnx + ix] = (int32_t)f;
-      identity = identity && (int64_t)f == iy * lnx + ix;
-      // interior fine walls must be open (boundary walls: w 0 bottom, 1 right, 2 top, 3 left)
-      const bool bnd[4] = {iy == 0, ix == lnx - 1, iy == lny - 1, ix == 0};
-      for (int w = 0; w < 4 && ok; ++w) ok = bnd[w] || s.fine_surface[4 * f + w] < 0;
-    }
-    if (ok) {
-      rthx::LatticeLayout L{};
-      L.nx = (int32_t)lnx;
-      L.ny = (int32_t)lny;
-      L.identity = identity ? 1 : 0;
-      auto a16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-      size_t off = a16(8 * xs.size());
-      L.off_ys = (int32_t)off;
-      off = a16(off + 8 * ys.size());
-      L.bytes = (int32_t)off;
-      L.inv_x = (double)lnx / (xs[lnx] - xs[0]);
-      L.inv_y = (double)lny / (ys[lny] - ys[0]);
-      // RTHX_LAT_GUESS_SCALE (tests): the first guess of the cell scaled.  The
-      // guess only seeds the exact search against xs / ys, so the counts are
-      // the same for any scale; a scale off 1 sends most rays through the
-      // LAT ray's fix-up block (rthx_device.h lat_ray_fixup).
-      if (const char* gs = rthx::knob("RTHX_LAT_GUESS_SCALE")) {
-        const double sc = std::strtod(gs, nullptr);
-        if (std::isfinite(sc) && sc > 0.0) {
-          L.inv_x *= sc;
-          L.inv_y *= sc;
-        }
-      }
-      std::vector<uint4> blob(off / 16);
-      char* b = reinterpret_cast<char*>(blob.data());
-      std::memset(b, 0, off);
-      std::memcpy(b, xs.data(), 8 * xs.size());
-      std::memcpy(b + L.off_ys, ys.data(), 8 * ys.size());
-      UP(blob.data(), blob.size(), D.lat_blob);
-      if (!identity) UP(map.data(), map.size(), D.lat_map);
-      D.lat = L;
-    }
-  }
-#undef UP
-  {
-    int r3 = upload(d, &d->D, 1, &d->d_dom, "domain record");
-    if (r3) return bail(r3);
-  }
-  *out = d;
+  d->n_emitters = (int64_t)s.n_surfaces + s.n_fine;
+  d->n_bins = s.n_bins;
+  d->uniform_beta.assign(s.uniform_beta, s.uniform_beta + s.n_bins);
+  d->beta_first = std::move(B.beta_first);
+  d->single_convex = B.single_convex;
+  d->axis_rect = B.axis_rect;
+  d->ml_mixed = std::move(B.ml_mixed);
+  d->d_mirror = const_cast<uint32_t*>(static_cast<const uint32_t*>(D.c_mirror));
+  d->c_nv.assign(s.coarse_nv, s.coarse_nv + nc);
+  d->c_xy.assign(s.coarse_xy, s.coarse_xy + 8 * nc);
+  d->c_solid = std::move(B.csolid);
+  *out = d.release();
   return RTHX_OK;
 }
 
 RTHX_EXPORT int rthx_domain_set_mirror_walls(rthx_domain* dom, const uint8_t* mirror) {
   if (!dom) return fail(RTHX_EINVAL, "null domain");
-  const size_t nc = dom->c_nv.size();
-  std::vector<uint32_t> mask(nc, 0u);
+  std::vector<uint32_t> mask;
   int64_t n = 0;
-  for (size_t c = 0; mirror && c < nc; ++c)
-    for (int w = 0; w < 4; ++w) {
-      if (!mirror[4 * c + w]) continue;
-      if (w >= dom->c_nv[c]) return fail(RTHX_EINVAL, "mirror flag on a wall the coarse polygon does not have");
-      if ((dom->c_solid[c] >> w) & 1u) return fail(RTHX_EINVAL, "mirror flag on a solid wall");
-      mask[c] |= 1u << w;
-      ++n;
-    }
-  // A flagged wall between two coarse polygons reflects from both sides: the
-  // neighbour's wall with the same two end points takes the flag too (unless
-  // it is solid, where the ray ends anyway).
-  if (n > 0 && nc > 1) {
-    typedef std::array<double, 4> Key;  // the wall's end points, the smaller first
-    auto key_of = [&](size_t c, int w) {
-      const double* v = dom->c_xy.data() + 8 * c;
-      const int w2 = (w + 1) % dom->c_nv[c];
-      const std::pair<double, double> a{v[2 * w], v[2 * w + 1]}, b{v[2 * w2], v[2 * w2 + 1]};
-      return a < b ? Key{a.first, a.second, b.first, b.second} : Key{b.first, b.second, a.first, a.second};
-    };
-    std::map<Key, std::vector<std::pair<size_t, int>>> walls;
-    for (size_t c = 0; c < nc; ++c)
-      for (int w = 0; w < dom->c_nv[c]; ++w) walls[key_of(c, w)].push_back({c, w});
-    const std::vector<uint32_t> flagged = mask;
-    for (size_t c = 0; c < nc; ++c)
-      for (int w = 0; w < dom->c_nv[c]; ++w)
-        if ((flagged[c] >> w) & 1u)
-          for (const auto& o : walls[key_of(c, w)])
-            if (!((dom->c_solid[o.first] >> o.second) & 1u)) mask[o.first] |= 1u << o.second;
-  }
+  std::string err;
+  if (const int rc = rthx::mirror_masks(dom->c_nv, dom->c_xy, dom->c_solid, mirror, mask, n, err)) return fail(rc, err);
   rthx::DeviceGuard keep_device;
   HIP_TRY(hipSetDevice(dom->device), "hipSetDevice");
   // (stream order: after every trace enqueued on this domain; the masks are
   // in place when the call returns)
-  HIP_TRY(hipMemcpyAsync(dom->d_mirror, mask.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, dom->stream),
+  HIP_TRY(hipMemcpyAsync(dom->d_mirror, mask.data(), mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice, dom->stream),
           "hipMemcpy mirror masks");
   HIP_TRY(hipStreamSynchronize(dom->stream), "mirror masks");
   dom->n_mirror = n;

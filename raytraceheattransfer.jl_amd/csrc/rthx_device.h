@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rthx_domain2d.h"
+
 // Device code sees the domain arrays as global-address-space pointers, so the
 // compiler emits global_load (not flat_load) and can use SGPR base addressing;
 // host code sees plain pointers (same layout).
@@ -22,112 +24,9 @@ namespace rthx {
 
 // ---------------------------------------------------------------------------
 // Flattened domain in HBM (DESIGN.md "Data layout in HBM").  One copy of this
-// record lives in device memory; kernels get its address.
+// record lives in device memory; kernels get its address.  The records it
+// points to and the LDS layouts it holds: rthx_domain2d.h.
 // ---------------------------------------------------------------------------
-struct DevGrid {
-  double ox, oy;        // origin
-  double inv_x, inv_y;  // 1/cell size in x and y
-  int32_t nx, ny;
-  int32_t cell_base;    // offset of this grid's cells in grid_cells (and grid_lists / 2)
-  int32_t reserved;
-};
-
-// Polygon record (128 B): vertices and unit inward normals
-// (calculateInwardNormal.jl:1-12), always 4 slots.  A triangle repeats its
-// last vertex in slot 3 and has a zero normal there, so every loop below runs
-// over 4 edges without a vertex-count test: the repeated vertex adds a
-// horizontal zero-length edge that never crosses (point in polygon), and the
-// zero normal gives |d.n| = 0 < 1e-10, which distToSurface2D treats as
-// parallel (no hit).
-struct alignas(16) DevPoly {
-  double x[4], y[4];
-  double nx[4], ny[4];
-};
-
-// Point-location cell record (built by rthx_grid.cpp, layout = CellRec):
-// code = (a0 x + b0 y + c0 < 0) | (a1 x + b1 y + c1 < 0) << 1 selects leaf[code]:
-// >= 0 polygon, -1 outside all polygons, -2 test the cell's candidate list.
-struct alignas(16) DevCell {
-  double a0, b0, c0;
-  double a1, b1, c1;
-  int32_t leaf[4];
-};
-
-constexpr int kCosTable = 256;  // cos/sin(2 pi j / 256), j < 256
-constexpr int kLogTable = 128;  // neg_log_tab entries
-constexpr int kLogTableOffset = 2 * kCosTable;
-constexpr int kTableDoubles = kLogTableOffset + 4 * kLogTable;
-// The kernels' LDS copy of the tables holds one more double: the launch's
-// TraceParams::inv_beta_uniform, which the free path reads at its point of
-// use (a kernel-argument double kept live across the ray loop is spilled
-// with the SGPRs loaded beside it and reloaded by v_readlane every ray).
-constexpr int kTabInvBeta = kTableDoubles;
-constexpr int kLdsTableDoubles = kTableDoubles + 1;
-
-// Byte layout of the coarse mesh as multi-polygon trace kernels stage it in
-// LDS (CLDS kernels): DevPoly records at 0, then fine grids,
-// bounding boxes, fine-polygon offsets, solid-wall masks, the coarse grid's
-// cell records and one beta per coarse polygon for the traced bin.  Every
-// offset is a multiple of 16.  bytes == 0: not staged (too large).
-struct CoarseLayout {
-  int32_t bytes;      // whole LDS block, beta included
-  int32_t blob_bytes; // copied from c_blob (everything before beta)
-  int32_t off_fgrid, off_bbox, off_first, off_solid, off_cells, off_beta;
-};
-
-// Lattice form of a single axis-aligned coarse rectangle whose fine cells
-// are the nx x ny rectangles [xs[i], xs[i+1]) x [ys[j], ys[j+1]) (meshQuad
-// on a rectangle, meshQuad.jl:139-179).  LAT kernels stage the blob in LDS:
-// xs[nx+1], ys[ny+1] (f64; every interior fine wall is open, the boundary
-// walls' surface indices come from f_surf).  Fine cell (i, j) is polygon
-// j nx + i when `identity`, else lat_map[j nx + i].  bytes == 0: not a
-// lattice.
-constexpr int kLatMaxDim = 4096;  // most boxes a side (host: no lattice beyond it); cell indices then fit 24-bit multiplies
-struct LatticeLayout {
-  int32_t bytes;             // blob bytes (multiple of 16)
-  int32_t nx, ny;
-  int32_t identity;
-  int32_t off_ys;
-  int32_t reserved[5];
-  double inv_x, inv_y;       // nx / (xs[nx] - xs[0]), ny / (ys[ny] - ys[0]): first guess of the cell
-};
-
-// Lattice form of a multi-polygon domain (MLAT kernels): the coarse polygons
-// are the ncx x ncy boxes of a coarse lattice (cxs, cys) and the fine
-// polygons of every coarse box are the boxes of one global fine lattice (xs,
-// ys) inside it, x fastest (meshQuad.jl:139-179) -- a layered medium such as
-// the greenhouse (67 layers of 201 x 3 cells: one 201 x 201 lattice).  Blob:
-// xs[nx+1], ys[ny+1], cxs[ncx+1], cys[ncy+1] (f64), cmap[ncy ncx] (i32:
-// coarse polygon of box b = cj ncx + ci), MCoarse[n_coarse], bsolid[nbox]
-// (u32: solid walls of box b), then (staged per bin from ml_bbeta) one beta
-// per box (-1 when the fine betas of its polygon differ).
-struct MCoarse {
-  int32_t first;     // first fine polygon
-  int32_t i0, j0;    // its fine lattice box
-  int32_t nxf, nyf;  // fine boxes per row / column
-  int32_t ci, cj;    // coarse lattice box
-  uint32_t solid;    // bit w: coarse wall w solid
-};
-
-struct MLatLayout {
-  int32_t bytes;       // LDS block incl. the betas (0: not a lattice)
-  int32_t blob_bytes;  // staged from ml_blob
-  int32_t nx, ny, ncx, ncy;
-  int32_t off_ys, off_cxs, off_cys, off_cmap, off_cinfo, off_bsolid, off_beta;
-  int32_t off_lay;     // one coarse column (ncx == 1): LayerRec[ncy + 2] (a sentinel, the layers, a sentinel) staged per bin after the betas; else 0
-  double inv_x, inv_y, inv_cx, inv_cy;  // first guesses of lattice_index
-};
-
-// One layer of a one-column lattice as walk_layers reads it: its bounds,
-// this bin's beta and its solid walls in one 32-byte LDS record (two
-// ds_read_b128 per segment).
-struct alignas(16) LayerRec {
-  double y0, y1;
-  double beta;     // -1: the fine betas of the layer differ (MIXED)
-  uint32_t solid;  // bit w: wall w solid
-  uint32_t pad;
-};
-
 struct DevDomain {
   int32_t n_coarse, n_fine, n_surfaces, n_bins;
   // coarse polygons
@@ -351,13 +250,12 @@ __host__ __device__ __forceinline__ double fma_cc(double z, double c1, double c2
 // S = -ln(u)/beta, traceRay.jl:25,79).  u = 2^k z with z in [0.6875, 1.375)
 // (so u near 1 keeps k = 0), table entry i = 7 bits of z below the exponent:
 // invc ~ 1/c (c = centre of the entry's z interval) and T = ln(invc) as
-// hi + lo (host, long double: fill_log_table).  Then r = z invc - 1 (one fma,
+// hi + lo (host, long double: fill_tables).  Then r = z invc - 1 (one fma,
 // |r| <= 2^-8) and -ln(u) = -k ln2 + T - log1p(r), log1p by its degree-7
 // Taylor polynomial (truncation < 2e-18 relative).  Within ~1 ulp of the
 // correctly rounded value (tests/test_numerics.py); no division, about a
-// third of the instructions of fdlibm's log.  u = 0 -> +inf.
-constexpr uint64_t kLogOff = 0x3FE6000000000000ull;  // bits of 0.6875
-
+// third of the instructions of fdlibm's log.  u = 0 -> +inf.  (kLogOff, the
+// bits of 0.6875: rthx_domain2d.h.)
 __host__ __device__ __forceinline__ double neg_log_tab(double u, const double* tab) {
   const uint64_t ix = dbits(u);
   const uint64_t tmp = ix - kLogOff;
@@ -553,7 +451,7 @@ __device__ __forceinline__ double dist_to_polygon(double px, double py, double d
 // (0,-1), (1,0), (0,1), (-1,0) -- calculateInwardNormal.jl:1-12 flips its
 // normal away from the polygon midpoint, so the stored "inward" normals
 // point out of the cell (the parameter num/den is the same either way);
-// rthx_domain_create checks the pattern.  The general expressions reduce
+// the domain build checks the pattern (rthx_domain2d_build.cpp canonical_rect).  The general expressions reduce
 // exactly: num_i = (v_i - p).n_i is py-y0, x1-px, y1-py, px-x0 and
 // den_i = d.n_i is -dy, dx, dy, -dx (products with +-1 and +-0 are exact), so
 // the same candidates, comparisons and first-index ties as dist_to_polygon,
@@ -684,8 +582,8 @@ __device__ __forceinline__ bool point_in_polygon(double px, double py, const Pol
 
 // findFace2D, findFace2D.jl:48-68 (grid :2-27, bbox fallback :30-45).
 // Polygons [first, first+count); returns local index or -1.
-// The grid is the device point-location grid built by rthx_domain_create
-// (rthx_grid.cpp, DESIGN.md "Point location"): each cell record splits the
+// The grid is the device point-location grid built by the domain build
+// (rthx_domain2d_build.cpp build_grids, rthx_grid.cpp, DESIGN.md "Point location"): each cell record splits the
 // cell by at most two polygon-edge lines into regions verified to lie in one
 // polygon each, so a lookup is two line tests for every lane; cells that do
 // not fit fall back to their candidate list and the point-in-polygon loop.

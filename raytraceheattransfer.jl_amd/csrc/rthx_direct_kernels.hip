@@ -98,7 +98,7 @@ __global__ __launch_bounds__(FAITHFUL ? kDirectThreads : kDirectMaxThreads) RTHX
   // Q.hist: Q.hist copies of the [3][n_elem] counters; wave v adds into copy
   // v % Q.hist (fewer lanes contend for one LDS address on small domains)
   extern __shared__ uint32_t hist[];
-  __shared__ double s_tab[kLdsTableDoubles];  // cos and log tables, inv_beta_uniform (rthx_device.h)
+  __shared__ double s_tab[kLdsTableDoubles];  // cos and log tables, inv_beta_uniform (rthx_domain2d.h)
   __shared__ SingleCoarse s_single;
   const DevDomain& D = *Dp;
   const int tid = threadIdx.x;

@@ -1,6 +1,6 @@
 // rthx_domain.h -- the opaque handles of include/rthx.h shared between
 // translation units: rthx_domain (the uploaded 2D domain, rthx_api.cpp
-// rthx_domain_create; used by the exchange tracer and the direct method,
+// rthx_domain_create, built by rthx_domain2d_build.h build_domain2d; used by the exchange tracer and the direct method,
 // rthx_direct.cpp) and rthx_result (an exchange trace's counts, filled by
 // rthx_trace_exchange and, through rthx_rowtrace.h, by the 3D tracer and the
 // gas-box tracer).
@@ -49,9 +49,10 @@ struct rthx_domain {
   bool axis_rect = false;            // every polygon an axis-aligned rectangle in canonical order (AXIS kernels)
   std::vector<uint8_t> ml_mixed;     // MLAT: per bin, 1 if some coarse box has no single beta (TraceParams::mixed)
   // rthx_domain_set_mirror_walls: the coarse polygons' vertex counts, vertices
-  // and solid masks (the setter's checks and its search for a flagged wall's
-  // neighbour), the device masks D.c_mirror points to (zero from
-  // rthx_domain_create on) and the number of walls the caller flagged
+  // and solid masks (rthx_domain2d_build.h mirror_masks: the setter's checks
+  // and its search for a flagged wall's neighbour), the device masks
+  // D.c_mirror points to (zero from rthx_domain_create on) and the number of
+  // walls the caller flagged
   std::vector<int32_t> c_nv;
   std::vector<double> c_xy;  // [n_coarse][4][2]
   std::vector<uint32_t> c_solid;

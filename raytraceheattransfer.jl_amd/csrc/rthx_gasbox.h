@@ -220,7 +220,7 @@ enum Tally : int { kU32 = 0, kU16 = 1, kGlobal = 2 };
 struct Launch {
   Box B;
   double beta;             // >= 0
-  const double* tables;    // kTableDoubles doubles (rthx_device.h), device memory
+  const double* tables;    // kTableDoubles doubles (rthx_domain2d.h), device memory
   int64_t R, ray_base;
   int64_t g_begin, g_stride, n_rows;
   int32_t split;

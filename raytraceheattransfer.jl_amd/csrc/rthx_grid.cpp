@@ -1,4 +1,5 @@
-// rthx_grid.cpp — host-side builder of the device point-location grid.
+// rthx_grid.cpp — host-side builder of the device point-location grid
+// (called per polygon set by rthx_domain2d_build.cpp build_grids).
 //
 // The reference locates a point with a uniform grid (cell size 2*sqrt(mean
 // area), spatialAccelerations.jl:2-59) whose cells list every polygon whose

@@ -16,7 +16,7 @@ constexpr int64_t kStaticLdsBytes = 10240;      // bound on the trace kernel's s
 // cold rays a row of the LAT ray's closed-enclosure copy lists: 512 bytes of static LDS (and a counter) in the six
 // PLAINK instances of the trace kernel, which alone use them; no other instance allocates them
 constexpr int kLatColdList = 128;
-constexpr size_t kMaxCoarseLdsBytes = 48 * 1024; // largest coarse mesh the CLDS kernels stage in LDS
+// (kMaxCoarseLdsBytes, the largest coarse mesh the CLDS kernels stage in LDS: rthx_domain2d.h)
 
 struct RecordParams {
   int32_t n;            // recorded emitters in this call

@@ -403,7 +403,7 @@ __device__ __forceinline__ void emit_ray(const Emit3& E, const double* tab, uint
 
 // Grid: n_rows * split workgroups; workgroup (slot, part) traces rays
 // [part * chunk, ...) of emitter g = g_begin + slot * g_stride.
-// TOP: breadth-first top nodes of the BVH (rthx_trace3d.cpp layout_nodes)
+// TOP: breadth-first top nodes of the BVH (rthx_scene3d_build.cpp layout_nodes)
 // staged in static LDS; the walk reads nodes < TOP there.  A small cache
 // serves the nodes most lanes share (larger ones measured slower: lanes
 // reading different deep nodes conflict in LDS banks).
@@ -457,7 +457,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MODE =
   const int64_t words = GH ? 0 : PACK16 ? (N + 1) / 2 : N;
   for (int64_t i = tid; i < words; i += kThreads) hist[i] = 0u;
   uint32_t* dense = T.dense + slot * N;
-  // breadth-first top of the BVH (rthx_trace3d.cpp layout_nodes)
+  // breadth-first top of the BVH (rthx_scene3d_build.cpp layout_nodes)
   {
     typedef float f4 __attribute__((ext_vector_type(4)));
     const f4 RTHX_GLOBAL* src = (const f4 RTHX_GLOBAL*)S.nodes;
